@@ -15,7 +15,13 @@ the timed region.  Total work per step is one frame whatever N is ("scaling": "s
 `torch.distributed.run` as a child process before anything touches a GPU and passes rank 0's
 line through.
 
-Prints ONE JSON line on rank 0 (contract in the task description).  Extra keys:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps frames and
+prints the headline figure (`value`, `ms_per_step`: the milliseconds one timed step took);
+--dump-outputs DIR also writes the last timed step's frame as DIR/frame.npy, so that two
+builds can be compared output for output (the inputs are seeded: the same in every run).
+Everything else -- the single-frame, moving-camera and static-pose phases, the roofline, the
+frame checks (`parity`, --group's `frame_check`) and the CPU baseline -- runs with --full only.
+Extra keys of a --full line:
   roofline      -- the frame's trace kernels (all bounces) against the VALU issue roof: the
                    kernel is instruction-issue bound.  achieved = VALU
                    wave-instructions per frame (rocprofv3 PMC SQ_INSTS_VALU, committed under
@@ -160,7 +166,41 @@ def parse(argv=None):
                     help="seconds any wait on a frame's gather may take before the run exits non-zero naming the "
                     "rank and the frame slot (process group timeout; gloo: each gather; --group: every frame wait)")
     ap.add_argument("--save", default="", help="rank 0: save the assembled frame (.pfm/.png)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run and report everything beside the headline figure: the "
+                    "single-frame, moving-camera and static-pose phases, trace-kernel times and the roofline, the "
+                    "frame checks against the reference shaders' hash (parity) and a single-context render "
+                    "(--group), the library hashes and the CPU baseline (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0: after the timed steps write the frame the last timed step produced as "
+                    "DIR/frame.npy (float32; a fixed seeded pixel sample with DIR/frame_index.npy when the frame "
+                    "exceeds 64 MB)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: every file of a run together
+DUMP_SAMPLE_SEED = 20240229  # ... the pixel sample of a larger frame: the same pixels in every run
+
+
+def dump_outputs(directory: str, frame) -> None:
+    """--dump-outputs: the frame of the last timed step (H, W, 3) as DIR/frame.npy, float32.  A
+    frame above DUMP_MAX_BYTES is written as a seeded sample of its pixels, (n, 3) in ascending
+    pixel order, with their flat indices y * W + x as DIR/frame_index.npy (float64: exact)."""
+    img = np.ascontiguousarray(frame.cpu().numpy() if hasattr(frame, "cpu") else frame, dtype=np.float32)
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    if img.nbytes > DUMP_MAX_BYTES:
+        npix = img.shape[0] * img.shape[1]
+        n = DUMP_MAX_BYTES // (3 * 4 + 8) - 64  # a pixel and its index, less the two .npy headers
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(npix, size=n, replace=False))
+        np.save(out / "frame_index.npy", idx.astype(np.float64))
+        img = img.reshape(npix, 3)[idx]
+    else:
+        (out / "frame_index.npy").unlink(missing_ok=True)  # (of an earlier, larger config)
+    np.save(out / "frame.npy", img)
 
 
 def free_port() -> int:
@@ -483,14 +523,17 @@ def _main():
     # the assembled static frame, kept on the device for the check against the reference's own
     # shaders at the end (hashing it here would pause the host long enough for the clocks to drop
     # before the single-frame phase)
-    parity_frame = frame.clone() if (rank == 0 and frame is not None and args.config in ("c1", "c2", "c3", "ref_default", "ref_stats114")) else None
+    parity_frame = frame.clone() if (args.full and rank == 0 and frame is not None and args.config in ("c1", "c2", "c3", "ref_default", "ref_stats114")) else None
+    # --dump-outputs: the same frame, kept on the device likewise and written after every phase
+    dump_frame = frame.clone() if (args.dump_outputs and rank == 0 and frame is not None) else None
     kern_ms = [a.elapsed_time(b) for a, b, _ in evs]       # whole per-frame pipeline (trace+shade+sort)
     latency_ms = [a.elapsed_time(c) for a, _, c in evs]    # render start -> frame gathered and assembled
-    nframes0 = min(-(-args.steps // inflight), 64)          # context 0's timed frames
-    first_trace_ms = r.trace_times_ms(nframes0)             # bounce-0 trace kernel of each frame
-    ftrace = r.frame_trace_times_ms(nframes0)               # every trace kernel of each frame, summed
-    trace_ms = [m for m, _ in ftrace]
-    launches = sorted({n for _, n in ftrace})
+    if args.full:
+        nframes0 = min(-(-args.steps // inflight), 64)      # context 0's timed frames
+        first_trace_ms = r.trace_times_ms(nframes0)         # bounce-0 trace kernel of each frame
+        ftrace = r.frame_trace_times_ms(nframes0)           # every trace kernel of each frame, summed
+        trace_ms = [m for m, _ in ftrace]
+        launches = sorted({n for _, n in ftrace})
     t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -502,7 +545,7 @@ def _main():
     # not part of `value`)
     single = None
     trace_ms_in_flight = None
-    if inflight > 1 and args.single_steps > 0:
+    if args.full and inflight > 1 and args.single_steps > 0:
         rs[0].set_split_heavy(-1)  # one frame in flight: the default (split walks on small tiles)
         sev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) for _ in range(args.single_steps)]
         # untimed warm-up frames of this setting: the first split frame of a context creates its
@@ -560,7 +603,7 @@ def _main():
     # context renders every frames_in_flight-th frame; after the main timed
     # region, not part of `value`)
     moving = None
-    if args.moving_steps > 0:
+    if args.full and args.moving_steps > 0:
         from octreeraytracer_amd.scene import DEFAULT_YAW
         poses = [ort.FrameParams.default_camera(W, H, num_samples=NS, max_depth=MAXD,
                                                 yaw=DEFAULT_YAW + args.yaw_step * (k + 1))
@@ -640,8 +683,6 @@ def _main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = rays_per_frame * args.steps / elapsed / 1e6
-        pmc = load_pmc(args, tile.rows)
-        kernels = trace_kernel_names(args.config, info, MAXD, NS, tile.rows * W)
         result = {
             "metric": metric_name(args.config),
             "value": round(value, 2),
@@ -671,6 +712,12 @@ def _main():
             # with frames in flight a frame's latency exceeds ms_per_step (its share of throughput)
             "frame_latency_ms_avg": round(float(np.mean(latency_ms)), 4),
             "frame_latency_ms_max": round(float(np.max(latency_ms)), 4),
+            "setup": setup,
+        }
+    if rank == 0 and args.full:  # everything beside the headline figure
+        pmc = load_pmc(args, tile.rows)
+        kernels = trace_kernel_names(args.config, info, MAXD, NS, tile.rows * W)
+        result.update({
             "single_frame": None if single is None else {
                 "frames_in_flight": 1, "steps": args.single_steps,
                 "value": round(rays_per_frame * args.single_steps / single[0] / 1e6, 2),
@@ -706,21 +753,23 @@ def _main():
             "first_trace_kernel_ms_min": round(float(np.min(first_trace_ms)), 4),
             "roofline": roofline(pmc, counts, (pmc or {}).get("traversals_per_frame"), alg_bytes,
                                  float(np.mean(trace_ms)), kernels),
-            "setup": setup,
             "parity": reference_frame_check(args.config, parity_frame, saved),
             "build_sha": lib_sha(),
             "device_sha": device_sha(),
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             if tree is None:
                 t0 = time.time()
                 tree = ort.build_octree(spheres, DEPTH, MPN)  # the oracle walks the host tree
                 setup["host_octree_build_s"] = round(time.time() - t0, 3)
             result["cpu_baseline"] = cpu_baseline(spheres, tree, p, args.cpu_seconds, args.cpu_threads)
+    if rank == 0:
         if args.save:
             img = saved
             from octreeraytracer_amd import image
             (image.write_png if args.save.endswith(".png") else image.write_pfm)(args.save, img)
+        if dump_frame is not None:
+            dump_outputs(args.dump_outputs, dump_frame)
     for x in rs:
         x.close()
     if world > 1:
@@ -797,27 +846,26 @@ def _group_bench(args):
     elapsed = time.perf_counter() - t0
     latency = g.last_frame_ms()  # the last frame: submission on devices[0] -> assembled
     last = outs[(args.steps - 1) % nslot]
-    frame = last.cpu().numpy()
+    frame = last.cpu().numpy() if args.full or args.dump_outputs else None
     # single-frame phase: one frame in flight at a time (render() = submit + wait), latency
     single = []
-    for _ in range(max(3, min(args.steps, 10))):
+    for _ in range(max(3, min(args.steps, 10)) if args.full else 0):
         t1 = time.perf_counter()
         g.render(p, out=outs[0])
         single.append((time.perf_counter() - t1) * 1e3)
     single_lat = g.last_frame_ms()
     counts = [g.count_traffic(p, r) for r in range(N)]
     rays_per_frame = sum(c["traversals"] for c in counts)
-    nframes0 = min(-(-args.steps // inflight), 64)
-    ftrace = g.frame_trace_times_ms(0, nframes0)
-    trace_ms = [m for m, _ in ftrace]
+    if args.full:
+        nframes0 = min(-(-args.steps // inflight), 64)
+        ftrace = g.frame_trace_times_ms(0, nframes0)
+        trace_ms = [m for m, _ in ftrace]
     info = None
-    with ort.Renderer(devices[0]) as ref:  # the frame check: one context, the whole frame
+    with ort.Renderer(devices[0]) as ref:  # the tree's figures; --full, the frame check: one context, the whole frame
         ref.build_scene(spheres, DEPTH, MPN)
         info = ref.info()
-        want = ref.render(p)
-    same = bool(np.array_equal(frame.view(np.uint32), want.view(np.uint32)))
-    pmc = load_pmc(args, 0)
-    alg_bytes = ort.algorithmic_bytes(counts[0])
+        want = ref.render(p) if args.full else None
+    same = not args.full or bool(np.array_equal(frame.view(np.uint32), want.view(np.uint32)))
     value = rays_per_frame * args.steps / elapsed / 1e6
     result = {
         "metric": metric_name(args.config),
@@ -846,21 +894,28 @@ def _group_bench(args):
             "rays": "traced rays (octree traversals), all bounces and ranks",
         },
         "frame_latency_ms": round(latency, 4),
-        "single_frame": {"frames_in_flight": 1, "ms_per_frame_wall": round(float(np.median(single)), 4),
-                         "value": round(rays_per_frame / float(np.median(single)) / 1e3, 2),
-                         "frame_latency_ms": round(single_lat, 4)},
-        "trace_kernels_ms_avg_rank0": round(float(np.mean(trace_ms)), 4),
-        "roofline": roofline(pmc, counts[0], (pmc or {}).get("traversals_per_frame"), alg_bytes,
-                             float(np.mean(trace_ms)),
-                             trace_kernel_names(args.config, info, MAXD, NS, W * -(-H // (16 * N)) * 16,
-                                                split_ok=inflight == 1 and not args.rehearse_one_gpu)),
-        "frame_check": ("bit-identical to a single-context ort_render of the same scene" if same
-                        else "MISMATCH against a single-context ort_render"),
-        "parity": reference_frame_check(args.config, None, np.asarray(frame)),
         "setup": setup,
-        "build_sha": lib_sha(),
-        "device_sha": device_sha(),
     }
+    if args.full:  # everything beside the headline figure
+        pmc = load_pmc(args, 0)
+        alg_bytes = ort.algorithmic_bytes(counts[0])
+        result.update({
+            "single_frame": {"frames_in_flight": 1, "ms_per_frame_wall": round(float(np.median(single)), 4),
+                             "value": round(rays_per_frame / float(np.median(single)) / 1e3, 2),
+                             "frame_latency_ms": round(single_lat, 4)},
+            "trace_kernels_ms_avg_rank0": round(float(np.mean(trace_ms)), 4),
+            "roofline": roofline(pmc, counts[0], (pmc or {}).get("traversals_per_frame"), alg_bytes,
+                                 float(np.mean(trace_ms)),
+                                 trace_kernel_names(args.config, info, MAXD, NS, W * -(-H // (16 * N)) * 16,
+                                                    split_ok=inflight == 1 and not args.rehearse_one_gpu)),
+            "frame_check": ("bit-identical to a single-context ort_render of the same scene" if same
+                            else "MISMATCH against a single-context ort_render"),
+            "parity": reference_frame_check(args.config, None, np.asarray(frame)),
+            "build_sha": lib_sha(),
+            "device_sha": device_sha(),
+        })
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, frame)
     g.close()
     print(json.dumps(result), flush=True)
     if not same:
@@ -933,7 +988,10 @@ def emulate(args, world, rank):
                           "scaling": "strong", "vs_baseline": None, "dtype": "f32",
                           "data": "EMULATION (host build of the kernel code, gloo): a control-path test, not a "
                                   "measurement", "config": {"workload": args.config, "width": W, "height": H},
-                          "frame_sha256": digest, "parity": reference_frame_check(args.config, frame)}), flush=True)
+                          "frame_sha256": digest,
+                          **({"parity": reference_frame_check(args.config, frame)} if args.full else {})}), flush=True)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame.numpy())
     if world > 1:
         dist.destroy_process_group()
 

@@ -99,3 +99,54 @@ def test_trace_kernel_names_follow_the_tile_rules(pixels, split_ok, pairs, split
     assert small[1].startswith("ort_sample_resolve") and small[2].startswith("ort_pixel_paths<0, false, ..., 2>")
     one = bench.trace_kernel_names("c2", {"tree_depth": 6, "n_nodes": 209_000}, 4, 1, 1920 * 1080)
     assert one == [one[0]] and one[0].startswith("ort_pixel_paths<0, false>")  # one sample: whole pixels
+
+
+def test_dump_outputs_whole_frame_and_seeded_sample(tmp_path):
+    """--dump-outputs: a frame within the size limit is written whole; a larger one as the same
+    seeded pixel sample in every run, with the pixels' flat indices, within the limit in all."""
+    import numpy as np
+    small = np.arange(5 * 7 * 3, dtype=np.float32).reshape(5, 7, 3)
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    got = np.load(tmp_path / "s" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    assert not (tmp_path / "s" / "frame_index.npy").exists()
+    h, w = 2401, 2399  # 69 MB of float32 RGB: above the limit, odd sizes
+    big = np.arange(h * w * 3, dtype=np.float32).reshape(h, w, 3)  # (exact below 2^24 only: compared to itself)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    idx = np.load(tmp_path / "a" / "frame_index.npy")
+    px = np.load(tmp_path / "a" / "frame.npy")
+    assert idx.dtype == np.float64 and px.dtype == np.float32 and px.shape == (len(idx), 3)
+    i = idx.astype(np.int64)
+    assert np.all(np.diff(i) > 0) and i[0] >= 0 and i[-1] < h * w and np.array_equal(i.astype(np.float64), idx)
+    assert np.array_equal(px, big.reshape(-1, 3)[i])
+    assert len(i) > 3_000_000  # most of what the limit allows
+    files = [tmp_path / "a" / n for n in ("frame.npy", "frame_index.npy")]
+    assert sum(f.stat().st_size for f in files) <= 64_000_000
+    for f in files:  # the same sample, byte for byte, in a second run
+        assert f.read_bytes() == (tmp_path / "b" / f.name).read_bytes()
+
+
+def test_plain_line_is_lean_and_full_adds_the_rest(tmp_path, monkeypatch, capsys):
+    """A plain run prints the headline keys only and, with --dump-outputs, writes the last step's
+    frame; --full adds the frame check (here through --emulate: the host build of the kernel code)."""
+    import json
+    import sys
+
+    import numpy as np
+    import octreeraytracer_amd as ort
+    from oracle import oracle
+    lines = {}
+    for extra in ([], ["--full"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--emulate", "--config", "c1", "--steps", "2",
+                                          "--warmup", "0", "--dump-outputs", str(tmp_path / "out")] + extra)
+        bench.main()
+        lines[bool(extra)] = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    for line in lines.values():
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["unit"] == "Mrays/s" and line["dtype"] == "f32"
+        assert line["higher_is_better"] is True and line["value"] > 0
+    assert "parity" not in lines[False] and lines[True]["parity"]["bit_identical"]
+    s = ort.random_spheres(100, 42)
+    ref = oracle.render(s, ort.build_octree(s, 4, 0), ort.FrameParams.default_camera(256, 256))
+    got = np.load(tmp_path / "out" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), ref.view(np.uint32))

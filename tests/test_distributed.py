@@ -185,7 +185,7 @@ def test_bench_self_launch(world):
     root = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", str(world), "--emulate", "--config", "c1",
-                        "--steps", "1", "--warmup", "0"], capture_output=True, text=True, env=env, timeout=240)
+                        "--steps", "1", "--warmup", "0", "--full"], capture_output=True, text=True, env=env, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     line = _bench_line(r.stdout)
     assert line["n_gpus"] == world and "EMULATION" in line["data"]

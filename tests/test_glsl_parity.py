@@ -33,6 +33,7 @@ A, so frames agree to rounding, not bit for bit:
     rounding level (<= 1e-6) -- a wrong formula in the oracle's bounce code would move most
     pixels, not a few percent."""
 import json
+import os
 from pathlib import Path
 
 import numpy as np
@@ -146,9 +147,11 @@ def test_oracle_bit_exact_to_reference_shader(ort, oracle, name):
 
 RUNNER = Path(__file__).resolve().parents[1] / "oracle" / "_ref" / "glsl_run"
 SHADERS = Path("/root/reference/shaders")
+# the runner built and the shaders readable by this user (False, not an error, where they are closed to it)
+REGENERATE = os.access(RUNNER, os.X_OK) and os.access(SHADERS / "octree_fragment_shader.glsl", os.R_OK)
 
 
-@pytest.mark.skipif(not (RUNNER.exists() and SHADERS.exists()), reason="needs oracle/_ref/glsl_run and /root/reference")
+@pytest.mark.skipif(not REGENERATE, reason="needs oracle/_ref/glsl_run and the reference's shaders")
 @pytest.mark.parametrize("name", ["c1", "debug", "brute_d4"])
 def test_fixtures_regenerate_bit_for_bit(name):
     """The fixtures are what the reference's shaders give now (llvmpipe is deterministic)."""
@@ -161,7 +164,7 @@ def test_fixtures_regenerate_bit_for_bit(name):
     assert np.array_equal(img.view(np.uint32), ref.view(np.uint32))
 
 
-@pytest.mark.skipif(not (RUNNER.exists() and SHADERS.exists()), reason="needs oracle/_ref/glsl_run and /root/reference")
+@pytest.mark.skipif(not REGENERATE, reason="needs oracle/_ref/glsl_run and the reference's shaders")
 @pytest.mark.parametrize("name", ["c1", "prebuilt_spp4_d8", "c2_spp2_d4", "m8_d7_odd_b2", "debug_pose", "c2tree_zoom1",
                                   "config_default"])
 def test_canonical_hashes_regenerate(name):
@@ -173,7 +176,7 @@ def test_canonical_hashes_regenerate(name):
     assert frame_sha(img) == CANON["cases"][name]["sha256"]
 
 
-@pytest.mark.skipif(not (RUNNER.exists() and SHADERS.exists()), reason="needs oracle/_ref/glsl_run and /root/reference")
+@pytest.mark.skipif(not REGENERATE, reason="needs oracle/_ref/glsl_run and the reference's shaders")
 def test_interpolated_pixel_centre_is_implementation_defined():
     """Why the canonical prelude reads gl_FragCoord: at 333x177 llvmpipe's interpolated FragCoord
     varying misses the exact pixel centre by an ulp on part of the frame, which reseeds those

@@ -40,7 +40,7 @@ def test_bench_ranks_assemble_the_c3_frame(c3_frame, world, tmp_path):
     out = tmp_path / "frame.pfm"
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--rehearse-one-gpu",
-                        "--config", "c3", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--save", str(out)],
+                        "--config", "c3", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--save", str(out)],
                        capture_output=True, text=True, env=env, timeout=100)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -57,12 +57,12 @@ def test_bench_ranks_assemble_the_c3_frame(c3_frame, world, tmp_path):
 
 @pytest.mark.parametrize("world,inflight", [(4, 2), (8, 0)])
 def test_bench_group_rehearsal_is_bit_identical(world, inflight):
-    """`bench.py --group --rehearse-one-gpu`: one process, the C-ABI group with `world` ranks on
+    """`bench.py --full --group --rehearse-one-gpu`: one process, the C-ABI group with `world` ranks on
     GPU 0 (device-copy gather), frames submitted with slots in flight; the line's frame check
     compares the last frame with a single-context render bit for bit."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, str(ROOT / "bench.py"), "--group", "--gpus", str(world), "--rehearse-one-gpu",
-           "--config", "c3", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"]
+           "--config", "c3", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline"]
     if inflight:
         cmd += ["--inflight", str(inflight)]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=110)
@@ -77,3 +77,30 @@ def test_bench_group_rehearsal_is_bit_identical(world, inflight):
     import bench
     assert line["config"]["frames_in_flight"] == (inflight or bench.default_inflight("c3", world))
     assert line["frame_latency_ms"] > 0 and line["single_frame"]["frame_latency_ms"] > 0
+
+
+def test_plain_run_is_lean_and_dumps_its_last_frame(ort, tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W`: the headline keys only (none of --full's phases,
+    checks or baselines), N timed steps, and with --dump-outputs the frame of the last timed step,
+    bit-identical to a single render of the same seeded scene -- so in every run."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--config", "c2", "--steps", "3",
+                        "--warmup", "2", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, env=env, timeout=100)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 2 and line["n_gpus"] == 1
+    assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["config"]["rays_per_step"] == 1920 * 1080
+    assert line["value"] == pytest.approx(1920 * 1080 / line["ms_per_step"] / 1e3, rel=1e-3)
+    for key in ("single_frame", "moving_camera", "roofline", "parity", "cpu_baseline", "build_sha", "device_sha"):
+        assert key not in line, key
+    s = ort.random_spheres(10_000, 42)
+    with ort.Renderer(0) as rr:
+        rr.build_scene(s, 6, 0)
+        want = rr.render(ort.FrameParams.default_camera(1920, 1080))
+    got = np.load(tmp_path / "out" / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == want.shape
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))

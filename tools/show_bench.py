@@ -1,5 +1,5 @@
-"""One summary line per bench.py JSON line: value, ms/step, roofline frac, PMC match, single-frame
-value, CPU baseline.  usage: python tools/show_bench.py BENCH.json [...]"""
+"""One summary line per bench.py JSON line: value, ms/step and, of a `bench.py --full` line, roofline
+frac, PMC match, single-frame value, CPU baseline (None for a plain run's line).  usage: python tools/show_bench.py BENCH.json [...]"""
 import json
 import sys
 
