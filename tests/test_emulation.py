@@ -121,6 +121,26 @@ def test_inverted_or_nan_boxes_take_the_exact_walk(ort, oracle):
         assert same_bits(img, oracle.render(s, u, p)), bad
 
 
+@pytest.mark.parametrize("name", ["deep11", "deep13", "grown", "forced"])
+def test_explicit_walk_on_the_gpu_suites_scenes(ort, oracle, scene_c2, name):
+    """The scenes of tests/test_gpu_explicit.py -- trees of 11 and 13 levels, C2's tree with grown
+    boxes, C2's own tree under the forced layout -- through the explicit walk on the host, with
+    samples and bounces; and what the compact layout says to each."""
+    from test_gpu_explicit import TWINS_TREES, explicit_scenes
+    s, t, d, refusal = explicit_scenes(scene_c2)[name]
+    if d is not None:
+        assert (t.n_nodes, t.n_indices) == TWINS_TREES[d]
+    p = ort.FrameParams.default_camera(160, 96, num_samples=3, max_depth=5)
+    ref = oracle.render(s, t, p)
+    img, _ = emulate_render_host(s, t, p, layout=L.ORT_LAYOUT_EXPLICIT)
+    assert same_bits(img, ref)
+    if refusal is None:
+        assert same_bits(emulate_render_host(s, t, p, layout=L.ORT_LAYOUT_COMPACT)[0], ref)
+    else:
+        with pytest.raises(ort.OrtError, match=refusal):
+            emulate_render_host(s, t, p, layout=L.ORT_LAYOUT_COMPACT)
+
+
 def extreme_root_scene(ort):
     """Sphere-root edge cases for the fast walk's quotient/sqrt shortcuts (render_core.h
     qdiv/qsqrt): the camera inside a sphere (near root negative, far root taken), a sphere

@@ -6,7 +6,8 @@
    oracle's -- and so to the HIP kernels' -- on every case of tests/golden/glsl/canonical.json:
    C1, the DEBUG scene, M=1, C2, the whole 1920x1080 C2 and 3840x2160 C3 bench frames, brute force at 4 bounces,
    the prebuilt scene at 4 samples x 8 bounces, C2 at 2 x 4 and (1920x1080) 4 x 8, depth-9/10
-   M=1 trees with bounces (the HIP deep kernels), the sphere-root edge cases, moved camera
+   M=1 trees with bounces (the HIP deep kernels), trees of 11 and 13 levels (the HIP explicit
+   layout; tests/test_gpu_explicit.py's twins scene), the sphere-root edge cases, moved camera
    positions (the DEBUG pose, inside and above the field) and zooms 1-30, and the reference's own
    configurations (config.h's default 800x600 16 x 8, stats.csv:114, stats_maxspheres0.csv:68).
    Only SHA-256s are stored.
@@ -60,6 +61,9 @@ def inputs(ort, c):
     elif c["scene"] == "extreme":
         from test_emulation import extreme_root_scene
         s = extreme_root_scene(ort)
+    elif c["scene"] == "twins":  # n seeded spheres and barely overlapping copies of the last k
+        from test_gpu_explicit import twins
+        s = twins(c["n"], 42, c["k"], c["gap"])
     else:
         s = ort.debug_spheres()
     t = ort.build_octree(s, c["depth"], c["m"])
@@ -166,7 +170,7 @@ def test_fixtures_regenerate_bit_for_bit(name):
 
 @pytest.mark.skipif(not REGENERATE, reason="needs oracle/_ref/glsl_run and the reference's shaders")
 @pytest.mark.parametrize("name", ["c1", "prebuilt_spp4_d8", "c2_spp2_d4", "m8_d7_odd_b2", "debug_pose", "c2tree_zoom1",
-                                  "config_default"])
+                                  "config_default", "explicit_d11_twins_b3", "explicit_d13_twins"])
 def test_canonical_hashes_regenerate(name):
     """The canonical-builtin hashes are what the reference's shaders give now."""
     import sys

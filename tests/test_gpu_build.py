@@ -54,16 +54,26 @@ def test_gpu_builder_matches_reference(ort, renderer, key):
 
 
 @pytest.mark.parametrize("n,d,m,seed", [(1, 4, 0, 1), (3, 0, 0, 2), (50, 3, -1, 3), (200, 7, 5, 4),
-                                        (1000, 11, 1, 5), (5000, 6, 100000, 6)])
+                                        ("twins", 11, 1, 42), (5000, 6, 100000, 6)])
 def test_gpu_builder_matches_host_builder(ort, renderer, n, d, m, seed):
     """Edge shapes: one sphere, depth 0, negative / huge maxSpheresPerNode (size_t compare),
-    a depth-11 tree (beyond the compact layout: explicit layout on the device)."""
-    s = ort.random_spheres(n, seed)
+    a depth-11 tree (beyond the compact layout: explicit layout on the device).  The last is
+    tests/test_gpu_explicit.py's scene of barely overlapping pairs: 1000 random spheres under a
+    depth limit of 11 stop splitting at 10 levels or fewer, and the compact layout takes them."""
+    if n == "twins":
+        from test_gpu_explicit import TWINS, TWINS_TREES, twins
+        assert (TWINS[1], m) == (seed, 1)
+        s = twins(*TWINS)
+    else:
+        s = ort.random_spheres(n, seed)
     host = ort.build_octree(s, d, m)
     renderer.build_scene(s, d, m, keep_tree=True)
     assert same_tree(renderer.export_octree(), host)
     depth = renderer.info()["tree_depth"]
     assert renderer.info()["layout"] == ("compact" if depth <= 10 else "explicit")
+    if n == "twins":
+        assert (host.n_nodes, host.n_indices) == TWINS_TREES[d]
+        assert depth == 11 and renderer.info()["layout"] == "explicit"
 
 
 def test_gpu_builder_coincident_and_touching_spheres(ort, renderer):

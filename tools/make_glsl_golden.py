@@ -128,6 +128,14 @@ CANON_EXTRA = {
     # the reference's float offsets then name wrong children)
     "deep_d9_m0_b2": dict(scene="random", n=10000, depth=9, m=0, W=320, H=180, spp=1, md=2, oct=1, dyaw=-8.0,
                           dpitch=3.0),
+    # trees deeper than the compact layout's 10 levels (the reference allows MAXDEPTH up to 4000): the
+    # HIP path's explicit layout, its stack walk and the unfused pipeline.  tests/test_gpu_explicit.py's
+    # twins scene: 100 spheres and copies of the last 8 moved 1.999 radii along +x, maxSpheresPerNode 1
+    # -- 19,473 nodes at depth 11, 67,097 at depth 13
+    "explicit_d11_twins_b3": dict(scene="twins", n=100, k=8, gap=1.999, depth=11, m=1, W=320, H=180, spp=2, md=3,
+                                  oct=1, dyaw=0.0, dpitch=0.0),
+    "explicit_d13_twins": dict(scene="twins", n=100, k=8, gap=1.999, depth=13, m=1, W=320, H=180, spp=1, md=2, oct=1,
+                               dyaw=0.0, dpitch=0.0),
 }
 PRELUDE = ROOT / "oracle" / "glsl_canonical_builtins.glsl"
 
@@ -147,6 +155,10 @@ def case_inputs(c):
         sys.path.insert(0, str(ROOT / "tests"))
         from test_emulation import extreme_root_scene
         s = extreme_root_scene(ort)
+    elif c["scene"] == "twins":
+        sys.path.insert(0, str(ROOT / "tests"))
+        from test_gpu_explicit import twins
+        s = twins(c["n"], 42, c["k"], c["gap"])
     else:
         s = ort.debug_spheres()
     t = ort.build_octree(s, c["depth"], c["m"])
