@@ -270,6 +270,38 @@ int ort_get_stream(const ort_ctx* ctx, void** stream);
 int ort_render(ort_ctx* ctx, const ort_params* params, const ort_tile* tile,
                float* rgb_out, int out_is_device, void* stream);
 
+/* Where and in which form ort_render_ex writes the tile.  The reference's shader writes FragColor
+ * into the GL default framebuffer (glsl:658-663), an 8-bit RGBA surface: ORT_FORMAT_RGBA8 is that
+ * surface's content, quantised by the kernel itself (each channel: NaN -> 0, clamp to [0, 1],
+ * x * 255 + 0.5 in float32, truncated -- the package's image.to_srgb8), 4 bytes per pixel in place
+ * of 12. */
+#define ORT_FORMAT_RGB32F 0   /* 3 floats per pixel (ort_render's) */
+#define ORT_FORMAT_RGBA8  1   /* 4 bytes per pixel: R, G, B, A = 255; each channel to_srgb8's rounding */
+#define ORT_PLACE_TILE  0     /* output row j is tile row j, column c is tile column c (ort_render's) */
+#define ORT_PLACE_FRAME 1     /* data is a full frame: the pixel (x, y) lands at row y, column x */
+typedef struct ort_output {
+    void*   data;
+    int32_t is_device;        /* != 0: data is a device pointer on ctx's device */
+    int32_t format;           /* ORT_FORMAT_* */
+    int32_t placement;        /* ORT_PLACE_* */
+    int32_t reserved;         /* 0 */
+    int64_t row_pitch_bytes;  /* 0: tight (tile width, or frame width with ORT_PLACE_FRAME, x bytes per pixel) */
+} ort_output;
+/* ort_render with the output described by *output: the pixel of output row R, column C is written
+ * at data + R * row_pitch_bytes + C * bytes per pixel; the bytes of a row past its pixels are left
+ * untouched.  ORT_PLACE_TILE: (R, C) = (tile row j, tile column), rows with y >= height written as
+ * zeros (all four bytes of an RGBA8 pixel, alpha included: a padding row stays recognisable).
+ * ORT_PLACE_FRAME: (R, C) = (y, x0 + column) in a frame of params->height rows, rows with
+ * y >= height not written at all -- several tiles (a group's bands) land in one frame without an
+ * assembly pass; device output only.  ORT_ERR_INVALID_ARG, before anything is launched, for an
+ * unknown format or placement, reserved != 0, a row_pitch_bytes that is not a multiple of 4, is
+ * below the row's bytes or is 2^31 or more, a data pointer that is not 4-byte aligned, and ORT_PLACE_FRAME with host
+ * output.  Host output with a pitch is copied with hipMemcpy2DAsync.  stream: as ort_render.
+ * ort_render(ctx, p, t, rgb_out, out_is_device, s) is this call with
+ * {rgb_out, out_is_device, ORT_FORMAT_RGB32F, ORT_PLACE_TILE, 0, 0}. */
+int ort_render_ex(ort_ctx* ctx, const ort_params* params, const ort_tile* tile, const ort_output* output,
+                  void* stream);
+
 /* Duration in milliseconds of the last ort_render's kernels (the whole per-frame pipeline),
  * from HIP events recorded on its stream.  Only valid once that stream has passed the frame. */
 int ort_last_kernel_ms(ort_ctx* ctx, float* ms);
@@ -360,6 +392,14 @@ int ort_group_wait(ort_group* group, int64_t ticket);
 int ort_group_set_timeout(ort_group* group, int64_t timeout_ms);
 /* submit + wait for it and every earlier frame: synchronous. */
 int ort_group_render(ort_group* group, const ort_params* params, float* rgb_out, int32_t out_is_device);
+/* ort_group_submit / ort_group_render in the given ORT_FORMAT_*: out receives the whole tight
+ * frame, width x height pixels of 12 (RGB32F) or 4 (RGBA8) bytes; the ranks render their bands in
+ * that format, so the band tiles, the exchange and the de-interleave move a third of the bytes
+ * with RGBA8.  ort_group_submit / ort_group_render are these calls with ORT_FORMAT_RGB32F. */
+int ort_group_submit_fmt(ort_group* group, const ort_params* params, void* out, int32_t out_is_device,
+                         int32_t format, int64_t* ticket);
+int ort_group_render_fmt(ort_group* group, const ort_params* params, void* out, int32_t out_is_device,
+                         int32_t format);
 /* Device time, on devices[0], of the frame the last ort_group_wait / ort_group_render waited
  * for: from its submission on devices[0]'s stream to its assembly (renders, gather,
  * de-interleave; HIP events), taken when that frame completed -- the frame's latency, not its

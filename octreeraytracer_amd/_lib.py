@@ -63,9 +63,18 @@ EXPORTED_SYMBOLS = (
     "ort_group_set_option", "ort_group_upload_scene", "ort_group_build_scene", "ort_group_render",
     "ort_group_last_frame_ms", "ort_group_create_pipelined", "ort_group_frames_in_flight", "ort_group_submit",
     "ort_group_wait", "ort_group_set_timeout",
+    "ort_render_ex", "ort_group_submit_fmt", "ort_group_render_fmt",
 )
 ORT_GROUP_TRANSPORT_RCCL = 0
 ORT_GROUP_TRANSPORT_COPY = 1
+# ort_output (ort_render_ex): the pixel format and where the tile's pixels land
+ORT_FORMAT_RGB32F = 0
+ORT_FORMAT_RGBA8 = 1
+ORT_PLACE_TILE = 0
+ORT_PLACE_FRAME = 1
+FORMATS = {"rgb32f": ORT_FORMAT_RGB32F, "rgba8": ORT_FORMAT_RGBA8}
+PLACEMENTS = {"tile": ORT_PLACE_TILE, "frame": ORT_PLACE_FRAME}
+FORMAT_BPP = {ORT_FORMAT_RGB32F: 12, ORT_FORMAT_RGBA8: 4}
 
 
 class OrtParams(C.Structure):
@@ -80,6 +89,13 @@ class OrtTile(C.Structure):
     _fields_ = [
         ("x0", C.c_int32), ("width", C.c_int32), ("y0", C.c_int32), ("rows", C.c_int32),
         ("band_height", C.c_int32), ("band_stride", C.c_int32),
+    ]
+
+
+class OrtOutput(C.Structure):
+    _fields_ = [
+        ("data", C.c_void_p), ("is_device", C.c_int32), ("format", C.c_int32), ("placement", C.c_int32),
+        ("reserved", C.c_int32), ("row_pitch_bytes", C.c_int64),
     ]
 
 
@@ -122,6 +138,7 @@ def _declare(lib, debug: str = "none"):
         "ort_last_build_ms": (C.c_int, [_vp, _fp]),
         "ort_get_stream": (C.c_int, [_vp, C.POINTER(C.c_void_p)]),
         "ort_render": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), _vp, C.c_int, _vp]),
+        "ort_render_ex": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(OrtOutput), _vp]),
         "ort_last_kernel_ms": (C.c_int, [_vp, _fp]),
         "ort_last_trace_ms": (C.c_int, [_vp, _fp]),
         "ort_trace_times_ms": (C.c_int, [_vp, C.c_int, _fp]),
@@ -152,11 +169,14 @@ def _declare(lib, debug: str = "none"):
         "ort_group_create_pipelined": (C.c_int, [_ip, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
         "ort_group_frames_in_flight": (C.c_int, [_vp]),
         "ort_group_submit": (C.c_int, [_vp, C.POINTER(OrtParams), _vp, C.c_int32, C.POINTER(C.c_int64)]),
+        "ort_group_submit_fmt": (C.c_int, [_vp, C.POINTER(OrtParams), _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+        "ort_group_render_fmt": (C.c_int, [_vp, C.POINTER(OrtParams), _vp, C.c_int32, C.c_int32]),
         "ort_group_wait": (C.c_int, [_vp, C.c_int64]),
         "ort_group_set_timeout": (C.c_int, [_vp, C.c_int64]),
         "ort_debug_group_emulate": (C.c_int, [_fp, _fp, _fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip, C.c_int64,
                                               C.c_int32, C.POINTER(OrtParams), _fp]),
         "ort_debug_fast_order": (C.c_int, [C.c_int32, _ip, C.POINTER(C.c_uint8)]),
+        "ort_debug_pack_rgba8": (C.c_int, [_fp, C.c_int64, C.POINTER(C.c_uint32)]),
         "ort_debug_trace_rays": (C.c_int, [_fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip, C.c_int64, _fp,
                                            C.c_int32, C.c_int32, _ip]),
         "ort_debug_split_rays": (C.c_int, [_fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip, C.c_int64, _fp,

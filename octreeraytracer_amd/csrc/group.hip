@@ -84,18 +84,20 @@ const Rccl& rccl(std::string& err) {
     return r;
 }
 
-// de-interleave: frame row y <- row group_src_row(y) of its rank's band tile
+// de-interleave: frame row y <- row group_src_row(y) of its rank's band tile, as 32-bit words
+// (wpp per pixel: 3 for RGB32F, 1 for RGBA8)
 struct SrcTable {
-    const float* tile[ORT_GROUP_MAX_DEVICES];
+    const uint32_t* tile[ORT_GROUP_MAX_DEVICES];
 };
-__global__ void __launch_bounds__(256) k_assemble(SrcTable src, int world, int width, int height, float* out) {
+__global__ void __launch_bounds__(256) k_assemble(SrcTable src, int world, int width, int height, int wpp,
+                                                  uint32_t* out) {
     const int y = blockIdx.x;
     if (y >= height) return;
     int rank, trow;
     ort::group_src_row(y, world, rank, trow);
-    const size_t n = 3 * (size_t)width;
-    const float* s = src.tile[rank] + (size_t)trow * n;
-    float* d = out + (size_t)y * n;
+    const size_t n = (size_t)wpp * (size_t)width;
+    const uint32_t* s = src.tile[rank] + (size_t)trow * n;
+    uint32_t* d = out + (size_t)y * n;
     for (size_t i = threadIdx.x; i < n; i += blockDim.x) d[i] = s[i];
 }
 
@@ -108,11 +110,12 @@ struct GroupSlot {
     std::vector<ort_ctx*> ctx;
     std::vector<hipStream_t> stream;   // each context's own stream
     std::vector<ncclComm_t> comm;      // RCCL: this slot's communicators (one gather at a time each)
-    std::vector<float*> tile;          // per rank, on its device: rows x W x 3
-    std::vector<float*> recv;          // on devices[0]: the band tiles of ranks 1..n-1
-    size_t tile_floats = 0;
-    float* frame = nullptr;            // devices[0]: the assembled frame (host output path)
-    size_t frame_floats = 0;
+    // the buffers are counted in 32-bit words: 3 per pixel (RGB32F) or 1 (RGBA8)
+    std::vector<uint32_t*> tile;       // per rank, on its device: rows x W pixels
+    std::vector<uint32_t*> recv;       // on devices[0]: the band tiles of ranks 1..n-1
+    size_t tile_words = 0;
+    uint32_t* frame = nullptr;         // devices[0]: the assembled frame (host output path)
+    size_t frame_words = 0;
     std::vector<hipEvent_t> done;      // per rank: its tile has been copied (copy transport)
     // devices[0]: the gather's stream -- the receives (RCCL) or the waits for the copies, then
     // the de-interleave -- so that the bands of ranks 1..N-1 land while rank 0 still renders
@@ -175,33 +178,33 @@ void free_buffers(ort_group* g, GroupSlot& S) {
         }
     S.tile.assign(g->n, nullptr);
     (void)hipSetDevice(g->dev.empty() ? 0 : g->dev[0]);
-    for (float* p : S.recv)
+    for (uint32_t* p : S.recv)
         if (p) (void)hipFree(p);
     S.recv.assign(g->n, nullptr);
     if (S.frame) (void)hipFree(S.frame);
     S.frame = nullptr;
-    S.tile_floats = 0;
-    S.frame_floats = 0;
+    S.tile_words = 0;
+    S.frame_words = 0;
 }
 
 // (Re)allocates a slot's buffers; the slot's previous frame is complete (ort_group_submit).
-int ensure_buffers(ort_group* g, GroupSlot& S, size_t tile_floats, size_t frame_floats) {
-    if (tile_floats > S.tile_floats) {
+int ensure_buffers(ort_group* g, GroupSlot& S, size_t tile_words, size_t frame_words) {
+    if (tile_words > S.tile_words) {
         free_buffers(g, S);
         for (int r = 0; r < g->n; ++r) {
             GCHK(g, hipSetDevice(g->dev[r]));
-            GCHK(g, hipMalloc(&S.tile[r], tile_floats * sizeof(float)));
+            GCHK(g, hipMalloc(&S.tile[r], tile_words * sizeof(uint32_t)));
         }
         GCHK(g, hipSetDevice(g->dev[0]));
-        for (int r = 1; r < g->n; ++r) GCHK(g, hipMalloc(&S.recv[r], tile_floats * sizeof(float)));
-        S.tile_floats = tile_floats;
+        for (int r = 1; r < g->n; ++r) GCHK(g, hipMalloc(&S.recv[r], tile_words * sizeof(uint32_t)));
+        S.tile_words = tile_words;
     }
-    if (frame_floats > S.frame_floats) {
+    if (frame_words > S.frame_words) {
         GCHK(g, hipSetDevice(g->dev[0]));
         if (S.frame) (void)hipFree(S.frame);
         S.frame = nullptr;
-        GCHK(g, hipMalloc(&S.frame, frame_floats * sizeof(float)));
-        S.frame_floats = frame_floats;
+        GCHK(g, hipMalloc(&S.frame, frame_words * sizeof(uint32_t)));
+        S.frame_words = frame_words;
     }
     return ORT_OK;
 }
@@ -429,8 +432,16 @@ int ort_group_build_scene(ort_group* g, const float* cr, const float* ma, const 
 }
 
 int ort_group_submit(ort_group* g, const ort_params* p, float* rgb_out, int32_t out_is_device, int64_t* ticket) {
+    return ort_group_submit_fmt(g, p, rgb_out, out_is_device, ORT_FORMAT_RGB32F, ticket);
+}
+
+int ort_group_submit_fmt(ort_group* g, const ort_params* p, void* rgb_out, int32_t out_is_device, int32_t format,
+                         int64_t* ticket) {
     if (!g || !p) return gfail(g, ORT_ERR_INVALID_ARG, "ort_group_submit: null argument");
     if (!rgb_out) return gfail(g, ORT_ERR_INVALID_ARG, "ort_group_submit: null output");
+    if (format != ORT_FORMAT_RGB32F && format != ORT_FORMAT_RGBA8)
+        return gfail(g, ORT_ERR_INVALID_ARG, "ort_group_submit: format: unknown ORT_FORMAT_*");
+    const size_t wpp = format == ORT_FORMAT_RGBA8 ? 1 : 3;  // 32-bit words per pixel
     if (p->width <= 0 || p->height <= 0) return gfail(g, ORT_ERR_INVALID_ARG, "ort_group_submit: width/height must be positive");
     const int W = p->width, H = p->height, N = g->n;
     const long long tk = g->next_ticket;
@@ -439,15 +450,16 @@ int ort_group_submit(ort_group* g, const ort_params* p, float* rgb_out, int32_t 
     // the slot's previous frame must be complete before its buffers are reused
     if ((rc = wait_slot(g, S))) return rc;
     const ort_tile t0 = ort::group_tile(W, H, 0, N);
-    const size_t tile_floats = (size_t)t0.rows * W * 3, frame_floats = (size_t)H * W * 3;
-    if ((rc = ensure_buffers(g, S, tile_floats, out_is_device ? 0 : frame_floats))) return rc;
+    const size_t tile_words = (size_t)t0.rows * W * wpp, frame_words = (size_t)H * W * wpp;
+    if ((rc = ensure_buffers(g, S, tile_words, out_is_device ? 0 : frame_words))) return rc;
     GCHK(g, hipSetDevice(g->dev[0]));
     GCHK(g, hipEventRecord(S.t0, S.stream[0]));
     // 1. every rank renders its bands on its own stream: ort_render with a stream never waits
     //    on the host (also for multi-bounce frames), so every rank is enqueued before any runs
     for (int r = 0; r < N; ++r) {
         const ort_tile t = ort::group_tile(W, H, r, N);
-        if ((rc = each(g, S.ctx[r], ort_render(S.ctx[r], p, &t, S.tile[r], 1, S.stream[r]), r))) return rc;
+        const ort_output o = {S.tile[r], 1, format, ORT_PLACE_TILE, 0, 0};
+        if ((rc = each(g, S.ctx[r], ort_render_ex(S.ctx[r], p, &t, &o, S.stream[r]), r))) return rc;
     }
     GCHK(g, hipSetDevice(g->dev[0]));
     GCHK(g, hipEventRecord(S.rendered0, S.stream[0]));
@@ -461,8 +473,9 @@ int ort_group_submit(ort_group* g, const ort_params* p, float* rgb_out, int32_t 
             const Rccl& R = rccl(why);
             ncclResult_t e = R.groupStart();
             for (int r = 1; r < N && e == ncclSuccess; ++r) {
-                e = R.send(S.tile[r], tile_floats, ncclFloat32, 0, S.comm[r], S.stream[r]);
-                if (e == ncclSuccess) e = R.recv(S.recv[r], tile_floats, ncclFloat32, r, S.comm[0], S.gstream);
+                // (words sent as ncclFloat32 in either format: send/recv copy bits, the type only sizes them)
+                e = R.send(S.tile[r], tile_words, ncclFloat32, 0, S.comm[r], S.stream[r]);
+                if (e == ncclSuccess) e = R.recv(S.recv[r], tile_words, ncclFloat32, r, S.comm[0], S.gstream);
             }
             const ncclResult_t e2 = R.groupEnd();
             if (e != ncclSuccess || e2 != ncclSuccess)
@@ -476,7 +489,7 @@ int ort_group_submit(ort_group* g, const ort_params* p, float* rgb_out, int32_t 
                 GCHK(g, hipSetDevice(g->dev[r]));
                 // recv[r] is free once this slot's previous assembly has read it
                 if (S.assembled_once) GCHK(g, hipStreamWaitEvent(S.stream[r], S.assembled, 0));
-                GCHK(g, hipMemcpyPeerAsync(S.recv[r], g->dev[0], S.tile[r], g->dev[r], tile_floats * sizeof(float),
+                GCHK(g, hipMemcpyPeerAsync(S.recv[r], g->dev[0], S.tile[r], g->dev[r], tile_words * sizeof(uint32_t),
                                            S.stream[r]));
                 GCHK(g, hipEventRecord(S.done[r], S.stream[r]));
                 GCHK(g, hipSetDevice(g->dev[0]));
@@ -490,14 +503,14 @@ int ort_group_submit(ort_group* g, const ort_params* p, float* rgb_out, int32_t 
     SrcTable src{};
     src.tile[0] = S.tile[0];
     for (int r = 1; r < N; ++r) src.tile[r] = S.recv[r];
-    float* dst = out_is_device ? rgb_out : S.frame;
-    hipLaunchKernelGGL(k_assemble, dim3((unsigned)H), dim3(256), 0, S.gstream, src, N, W, H, dst);
+    uint32_t* dst = out_is_device ? (uint32_t*)rgb_out : S.frame;
+    hipLaunchKernelGGL(k_assemble, dim3((unsigned)H), dim3(256), 0, S.gstream, src, N, W, H, (int)wpp, dst);
     GCHK(g, hipGetLastError());
     GCHK(g, hipEventRecord(S.assembled, S.gstream));
     S.assembled_once = true;
     GCHK(g, hipEventRecord(S.t1, S.gstream));
     if (!out_is_device)  // pageable rgb_out: the runtime may stage this copy synchronously
-        GCHK(g, hipMemcpyAsync(rgb_out, S.frame, frame_floats * sizeof(float), hipMemcpyDeviceToHost, S.gstream));
+        GCHK(g, hipMemcpyAsync(rgb_out, S.frame, frame_words * sizeof(uint32_t), hipMemcpyDeviceToHost, S.gstream));
     GCHK(g, hipEventRecord(S.finished, S.gstream));
     S.ticket = tk;
     g->next_ticket = tk + 1;
@@ -527,8 +540,12 @@ int ort_group_set_timeout(ort_group* g, int64_t timeout_ms) {
 }
 
 int ort_group_render(ort_group* g, const ort_params* p, float* rgb_out, int32_t out_is_device) {
+    return ort_group_render_fmt(g, p, rgb_out, out_is_device, ORT_FORMAT_RGB32F);
+}
+
+int ort_group_render_fmt(ort_group* g, const ort_params* p, void* rgb_out, int32_t out_is_device, int32_t format) {
     int64_t tk = -1;
-    int rc = ort_group_submit(g, p, rgb_out, out_is_device, &tk);
+    int rc = ort_group_submit_fmt(g, p, rgb_out, out_is_device, format, &tk);
     if (rc) return rc;
     // synchronous, like ort_render without a stream: every earlier frame has completed too
     for (GroupSlot& S : g->slot)

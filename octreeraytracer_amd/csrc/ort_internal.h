@@ -35,6 +35,9 @@ int ort_debug_group_emulate(const float* sphere_center_radius, const float* sphe
 // rows (rank_lut_entry) for every child mask: lut256[cmask] (checked against the shader's
 // tables, tests/golden/traversal_orders.json).
 int ort_debug_fast_order(int32_t m, int32_t* order8, uint8_t* lut256);
+// TEST-ONLY: the kernels' RGBA8 quantiser (render_core.h pack_rgba8) on the host: out[i] = the
+// packed word of the pixel rgb[3 i .. 3 i + 2] (checked against image.to_srgb8).
+int ort_debug_pack_rgba8(const float* rgb, int64_t n_pixels, uint32_t* out);
 // TEST-ONLY: the split walk (render_core.h traverse_split, the walk of ort_trace_split) of each
 // ray run by `lanes` lanes one after another, level-`level` subtrees dealt round robin, merged by
 // the lowest DFS position; out[4 i] = {hit entry (-1 none), t bits, position, summed steps}.

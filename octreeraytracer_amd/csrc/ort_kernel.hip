@@ -90,7 +90,7 @@ struct PipeArgs {
     float4* pc;       // path throughput c.xyz
     float2* prng;     // randState
     float4* pcol;     // running sum of samples
-    float* out;
+    void* out;        // the output (ort_output; out_pitch, out_format, out_place below)
     unsigned long long* counters;
     uint16_t* pcost;  // ORT_OPT_COST_ORDER: per slot, the walk steps of its last camera ray, or null
     uint16_t* bcost_w;        // ORT_OPT_HEAVY_FIRST: the persistent bounce trace records each walk's steps here
@@ -147,6 +147,12 @@ struct PipeArgs {
     int* fx_s0;
     float2* fx_st;
     float* fx_col;
+    // the output description (store_pixel / store_padding): the pixel of output row R, column C at
+    // out + R * out_pitch + C * bytes per pixel.  (Last, so that the fields above keep their places
+    // in the kernel argument segment: the tuned kernels load them in the same groups as before.)
+    unsigned out_pitch;   // bytes per output row (32 bits: a row's address is one 32 x 32 -> 64 bit multiply-add)
+    int out_format;       // ORT_FORMAT_*
+    int out_place;        // ORT_PLACE_*
 #if ORT_ANALYSIS
     ulonglong4* wclock;  // analysis builds only (ORT_PERSIST_CLOCK, ort_debug_wave_clock): per wave a timeline record
     int wclock_n;
@@ -575,6 +581,81 @@ __device__ inline ort::Ray slot_ray(const PipeArgs& A, int k, bool& alive, ort_r
     }
 }
 
+// Every pixel leaves the kernels through store_pixel / store_padding.  The format and the
+// placement are wave-uniform kernel arguments: scalar branches.
+// out_coords: the output row and column of tile row `row`, tile column `col` -- themselves under
+// tile placement, the pixel's (y, x) under frame placement (y < 0 where the site does not hold the
+// pixel row: derived).  PLAIN: compiled for ort_render's own output (RGB32F, tile placement, tight
+// rows) alone -- ort_shade_kernel's bounce-0 instance, whose scalar registers the output
+// description would overflow (8 -> 7 waves per SIMD).
+template <bool PLAIN = false>
+__device__ __forceinline__ void out_coords(const PipeArgs& A, int row, int col, int y, int& orow, int& ocol) {
+    orow = row;
+    ocol = col;
+    if (!PLAIN && A.out_place == ORT_PLACE_FRAME) {  // the pixel (x, y) at row y, column x of a whole frame
+        orow = y < 0 ? tile_row_to_y(A.tm, row) : y;
+        ocol = A.tm.x0 + col;
+    }
+}
+// The finished pixel v at output row orow, column ocol (out_coords).
+template <bool PLAIN = false>
+__device__ __forceinline__ void store_at(const PipeArgs& A, int orow, int ocol, ort::V3 v) {
+    if (PLAIN) {
+        float* o = (float*)A.out + 3 * ((size_t)orow * A.tm.tw + ocol);
+        o[0] = v.x;
+        o[1] = v.y;
+        o[2] = v.z;
+        return;
+    }
+    char* o8 = (char*)A.out + (size_t)(unsigned)orow * A.out_pitch;
+    if (A.out_format == ORT_FORMAT_RGBA8) {
+        *(uint32_t*)(o8 + 4u * (unsigned)ocol) = ort::pack_rgba8(v);
+    } else {
+        float* o = (float*)(o8 + 12u * (unsigned)ocol);
+        // plain stores (one global_store_dwordx3): non-temporal ones ran no faster and, their
+        // partial 64-byte lines written out unmerged, moved 1.38x the frame's bytes (PMC WRITE_SIZE)
+        o[0] = v.x;
+        o[1] = v.y;
+        o[2] = v.z;
+    }
+}
+// store_pixel: the finished pixel v of tile row `row`, tile column `col` (a pixel of the frame:
+// its row y < H at every site; y < 0 where the site does not hold it).
+__device__ __forceinline__ void store_pixel(const PipeArgs& A, int row, int col, int y, ort::V3 v) {
+    int orow, ocol;
+    out_coords(A, row, col, y, orow, ocol);
+    if (A.out_place == ORT_PLACE_FRAME && orow >= A.pp.H) return;  // (the frame's bound, kept here too)
+    store_at(A, orow, ocol, v);
+}
+// The kernel's arguments read again from the kernel argument segment through a laundered pointer
+// (as trace_slot does for its shading): for a store at the end of a long loop, so that the output
+// description is not held in scalar registers across it.  Kernels whose first argument is PipeArgs.
+__device__ __forceinline__ PipeArgs reread_args(const PipeArgs& A) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((address_space(4))) const PipeArgs KernArgs;
+    KernArgs* kp = (KernArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    return *kp;
+#else
+    return A;
+#endif
+}
+
+// A tile row past the frame (band padding, y >= H): zeros under tile placement (an RGBA8 pixel's
+// four bytes, alpha included: the row stays recognisable); under frame placement it lies outside
+// the frame and nothing is written.
+__device__ __forceinline__ void store_padding(const PipeArgs& A, int row, int col) {
+    if (A.out_place == ORT_PLACE_FRAME) return;
+    if (A.out_format == ORT_FORMAT_RGBA8) {
+        *(uint32_t*)((char*)A.out + ((size_t)(unsigned)row * A.out_pitch + 4u * (unsigned)col)) = 0u;
+    } else {
+        float* o = (float*)((char*)A.out + ((size_t)(unsigned)row * A.out_pitch + 12u * (unsigned)col));
+        o[0] = 0.0f;
+        o[1] = 0.0f;
+        o[2] = 0.0f;
+    }
+}
+
 // 1 sample, 1 bounce (the primary-ray benchmark mode): the trace kernels shade their own
 // rays -- exactly ort_shade_kernel<0, true, true> -- instead of writing hit records for it.
 template <int UNI = 0>
@@ -587,30 +668,22 @@ __device__ inline void shade_direct(const PipeArgs& A, int k, ort::Ray ray, ort_
     if (hit) rec = ort::hit_record<0>(A.S, ray, t, entry);
     (void)ort::shade_bounce<true>(hit, rec, ray, c, importance, st);  // 1 sample, 1 bounce: final
     const ort::V3 v = ort::finish_pixel(ort::add(ort::mk(0.0f, 0.0f, 0.0f), c), 1);
-    float* o = A.out + 3 * ((size_t)row * A.tm.tw + col);
-    // plain stores (one global_store_dwordx3): non-temporal ones ran no faster and, their
-    // partial 64-byte lines written out unmerged, moved 1.38x the frame's bytes (PMC WRITE_SIZE)
-    o[0] = v.x;
-    o[1] = v.y;
-    o[2] = v.z;
+    store_pixel(A, row, col, -1, v);
 }
 // Tile rows past the frame (band padding) are written as zeros, as the shade kernel does.
 template <int UNI = 1>
 __device__ inline void shade_direct_padding(const PipeArgs& A, int k) {
     int col, row;
     if (!slot_coords<UNI>(A, k, col, row) || tile_row_to_y(A.tm, row) < A.pp.H) return;
-    float* o = A.out + 3 * ((size_t)row * A.tm.tw + col);
-    o[0] = 0.0f;
-    o[1] = 0.0f;
-    o[2] = 0.0f;
+    store_padding(A, row, col);
 }
 
 // The shading proper of path slot k, given its ray and RNG state and the walk's result
 // (entry < 0: no hit); shared by ort_shade_kernel and the trace kernels that shade bounce 0
 // themselves.  Returns true when the path goes on to the next bounce.
-template <int MODE, bool FIRST, bool DIRECT>
-__device__ __forceinline__ bool shade_state(const PipeArgs& A, int k, size_t p, ort::Ray ray, ort_rng st, int entry,
-                                            float t) {
+template <int MODE, bool FIRST, bool DIRECT, bool PLAIN = false>
+__device__ __forceinline__ bool shade_state(const PipeArgs& A, int k, int orow, int ocol, ort::Ray ray, ort_rng st,
+                                            int entry, float t) {
     ort::V3 c = ort::mk(1.0f, 1.0f, 1.0f);
     float importance = 1.0f;
     if (!FIRST) {
@@ -630,8 +703,7 @@ __device__ __forceinline__ bool shade_state(const PipeArgs& A, int k, size_t p, 
     }
     if constexpr (DIRECT) {
         const ort::V3 v = ort::finish_pixel(ort::add(ort::mk(0.0f, 0.0f, 0.0f), c), 1);
-        float* o = A.out + 3 * p;
-        o[0] = v.x; o[1] = v.y; o[2] = v.z;
+        store_at(A, orow, ocol, v);
     } else {
         // the last sample of a final_out frame: a path that ends here writes its pixel and
         // nothing else -- the later kernels walk the lists of alive paths only, and no sample
@@ -646,8 +718,7 @@ __device__ __forceinline__ bool shade_state(const PipeArgs& A, int k, size_t p, 
             acc = ort::add(acc, c);
             if (fin) {  // ort_finalize_kernel's work for this pixel
                 const ort::V3 v = ort::finish_pixel(acc, A.pp.ns);
-                float* o = A.out + 3 * p;
-                o[0] = v.x; o[1] = v.y; o[2] = v.z;
+                store_at<PLAIN>(A, orow, ocol, v);
             } else {
                 A.pcol[k] = make_float4(acc.x, acc.y, acc.z, 0.0f);
                 A.pd[k] = make_float4(ray.d.x, ray.d.y, ray.d.z, 0.0f);
@@ -804,7 +875,8 @@ __device__ __forceinline__ bool trace_slot(PipeArgs& A, LdsView& L, int k, ort::
         } else {
             int col, row;
             (void)slot_coords<UNI>(A2, k2, col, row);
-            return shade_state<0, true, false>(A2, k2, (size_t)row * A2.tm.tw + col, walked, rng0, hit ? entry : -1, t);
+            out_coords(A2, row, col, -1, row, col);
+            return shade_state<0, true, false>(A2, k2, row, col, walked, rng0, hit ? entry : -1, t);
         }
     } else {
         A.hit[k] = make_int2(hit ? entry : -1, __float_as_int(t));
@@ -1201,7 +1273,8 @@ __global__ void __launch_bounds__(kBlock) ort_trace_split(PipeArgs A) {
             } else {  // bounce 0 of a multi-bounce frame: path state, and the next bounce's list
                 int col, row;
                 (void)slot_coords(A, k, col, row);
-                if (shade_state<0, true, false>(A, k, (size_t)row * A.tm.tw + col, ray, rng0, pos != kNoHit ? entry : -1, t)) {
+                out_coords(A, row, col, -1, row, col);
+                if (shade_state<0, true, false>(A, k, row, col, ray, rng0, pos != kNoHit ? entry : -1, t)) {
                     const int q = atomicAdd(A.qnext_count, 1);
                     A.qnext[q] = k;
                     if (A.qnext_keys)
@@ -1276,7 +1349,8 @@ __global__ void __launch_bounds__(kBlock) ort_trace_exact(PipeArgs A) {
         } else if (FUSE == 2) {  // bounce 0 shaded here; the rare deferred path joins the list alone
             int col, row;
             (void)slot_coords(A, k, col, row);
-            if (shade_state<0, true, false>(A, k, (size_t)row * A.tm.tw + col, ray, rng, st == ORT_TRACE_HIT ? entry : -1, t)) {
+            out_coords(A, row, col, -1, row, col);
+            if (shade_state<0, true, false>(A, k, row, col, ray, rng, st == ORT_TRACE_HIT ? entry : -1, t)) {
                 const int pos = atomicAdd(A.qnext_count, 1);
                 A.qnext[pos] = k;
                 if (A.qnext_keys)
@@ -1292,17 +1366,13 @@ __global__ void __launch_bounds__(kBlock) ort_trace_exact(PipeArgs A) {
 // Bounce shading (glsl:607-627) of path slot k.  FIRST: bounce 0 (c = 1, importance = 1).
 // DIRECT (1 sample, 1 bounce): writes the final pixel.  Returns true when the path goes on
 // to the next bounce.
-template <int MODE, bool FIRST, bool DIRECT>
+template <int MODE, bool FIRST, bool DIRECT, bool PLAIN = false>
 __device__ __forceinline__ bool shade_slot(const PipeArgs& A, int k) {
     int col, row;
     const bool in_tile = FIRST ? slot_coords<true>(A, k, col, row) : slot_coords(A, k, col, row);
     const int y = in_tile ? tile_row_to_y(A.tm, row) : 0;
-    const size_t p = (size_t)row * A.tm.tw + col;
     if (!in_tile || y >= A.pp.H) {
-        if (DIRECT && in_tile) {
-            float* o = A.out + 3 * p;
-            o[0] = 0.0f; o[1] = 0.0f; o[2] = 0.0f;
-        }
+        if (DIRECT && in_tile) store_padding(A, row, col);
         if (FIRST && !DIRECT) A.pd[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // never alive (compaction)
         return false;
     }
@@ -1327,14 +1397,16 @@ __device__ __forceinline__ bool shade_slot(const PipeArgs& A, int k) {
     }
     int2 h = make_int2(-1, 0);
     if (!A.nobounce) h = A.hit[k];
-    return shade_state<MODE, FIRST, DIRECT>(A, k, p, ray, st, h.x, __int_as_float(h.y));
+    int orow, ocol;
+    out_coords<PLAIN>(A, row, col, y, orow, ocol);
+    return shade_state<MODE, FIRST, DIRECT, PLAIN>(A, k, orow, ocol, ray, st, h.x, __int_as_float(h.y));
 }
 
 
 // Shades every path slot of its workgroup (slot order); with A.qnext, the paths that go on
 // are appended to the next bounce's list (the compaction, without a separate select pass).
-template <int MODE, bool FIRST, bool DIRECT>
-__global__ void __launch_bounds__(kBlock) ort_shade_kernel(PipeArgs A) {
+template <int MODE, bool FIRST, bool DIRECT, bool PLAIN>
+__device__ __forceinline__ void shade_kernel_body(const PipeArgs& A) {
     int k = blockIdx.x * kBlock + threadIdx.x;
     bool in = true;
     if (!FIRST && A.qlist) {  // the bounce's alive paths in append order (not the sorted trace list)
@@ -1343,13 +1415,24 @@ __global__ void __launch_bounds__(kBlock) ort_shade_kernel(PipeArgs A) {
         in = k < n;
         if (in) k = A.qlist[k];
     }
-    const bool go = in && shade_slot<MODE, FIRST, DIRECT>(A, k);
+    const bool go = in && shade_slot<MODE, FIRST, DIRECT, PLAIN>(A, k);
     if (!DIRECT && A.qnext) {
         uint32_t key = 0;
         if (go && A.qnext_keys)  // the state just stored
             key = path_key_class(A, k);
         append_slots(go, k, key, A.qnext, A.qnext_keys, A.qnext_count);
     }
+}
+// The bounce-0 instance (FIRST, not DIRECT) is compiled for ort_render's own output alone (RGB32F,
+// tile placement, tight rows); a frame of any other output runs ort_shade_first_any for that
+// bounce (launch_shade_mode).
+template <int MODE, bool FIRST, bool DIRECT>
+__global__ void __launch_bounds__(kBlock) ort_shade_kernel(PipeArgs A) {
+    shade_kernel_body<MODE, FIRST, DIRECT, FIRST && !DIRECT>(A);
+}
+template <int MODE>
+__global__ void __launch_bounds__(kBlock) ort_shade_first_any(PipeArgs A) {
+    shade_kernel_body<MODE, true, false, false>(A);
 }
 
 // col / ns, gamma (glsl:659-661) for the multi-sample / multi-bounce case.
@@ -1358,9 +1441,8 @@ __global__ void __launch_bounds__(kBlock) ort_finalize_kernel(PipeArgs A) {
     int col, row;
     if (!slot_coords<true>(A, k, col, row)) return;
     const int y = tile_row_to_y(A.tm, row);
-    float* o = A.out + 3 * ((size_t)row * A.tm.tw + col);
     if (y >= A.pp.H) {
-        o[0] = 0.0f; o[1] = 0.0f; o[2] = 0.0f;
+        store_padding(A, row, col);
         return;
     }
     ort::V3 acc = ort::mk(0.0f, 0.0f, 0.0f);
@@ -1368,8 +1450,7 @@ __global__ void __launch_bounds__(kBlock) ort_finalize_kernel(PipeArgs A) {
         const float4 a = A.pcol[k];
         acc = ort::mk(a.x, a.y, a.z);
     }
-    const ort::V3 v = ort::finish_pixel(acc, A.pp.ns);
-    o[0] = v.x; o[1] = v.y; o[2] = v.z;
+    store_pixel(A, row, col, y, ort::finish_pixel(acc, A.pp.ns));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1595,8 +1676,7 @@ ort_pixel_paths(PipeArgs A) {
                                 ray = ort::primary_ray(A.pp, px, py, s, st);
                                 pixel = true;
                             } else if (!SPEC) {  // a band's padding row (past the frame): zeros, as the pipeline writes
-                                float* o = A.out + 3 * ((size_t)cy * A.tm.tw + cx);
-                                o[0] = 0.0f; o[1] = 0.0f; o[2] = 0.0f;
+                                store_padding(reread_args(A), cy, cx);
                             }
                         }
                         if (ORT_PIXEL_LPT && !SPEC && A.pl_w && !pixel) block_account(A, cand, 0);
@@ -1654,9 +1734,7 @@ ort_pixel_paths(PipeArgs A) {
                 } else {
                     int cx, cy;
                     (void)slot_coords(A, k, cx, cy);
-                    const ort::V3 v = ort::finish_pixel(col, ns);
-                    float* o = A.out + 3 * ((size_t)cy * A.tm.tw + cx);
-                    o[0] = v.x; o[1] = v.y; o[2] = v.z;
+                    store_pixel(reread_args(A), cy, cx, py, ort::finish_pixel(col, ns));
                     if (ORT_PIXEL_LPT && A.pl_w) block_account(A, k, nb);  // its block's cost for the next frame
                     k = -1;
                 }
@@ -1702,9 +1780,8 @@ __global__ void __launch_bounds__(256) ort_sample_resolve(PipeArgs A) {
     if (k >= A.total) return;
     int cx, cy;
     if (!slot_coords(A, k, cx, cy)) return;
-    float* o = A.out + 3 * ((size_t)cy * A.tm.tw + cx);
     if (tile_row_to_y(A.tm, cy) >= A.pp.H) {
-        o[0] = 0.0f; o[1] = 0.0f; o[2] = 0.0f;
+        store_padding(A, cy, cx);
         return;
     }
     const int ns = A.pp.ns;
@@ -1737,8 +1814,7 @@ __global__ void __launch_bounds__(256) ort_sample_resolve(PipeArgs A) {
         col = ort::add(col, ort::mk(A.sp_col[i], A.sp_col[plane + i], A.sp_col[2 * plane + i]));
     }
     if (last == ns - 1) {
-        const ort::V3 v = ort::finish_pixel(col, ns);
-        o[0] = v.x; o[1] = v.y; o[2] = v.z;
+        store_pixel(A, cy, cx, -1, ort::finish_pixel(col, ns));
         return;
     }
     const int e = atomicAdd(A.fx_n, 1);
@@ -2294,7 +2370,10 @@ hipError_t launch_trace(int mode, bool primary, const PipeArgs& a, int blocks, i
 template <int MODE>
 hipError_t launch_shade_mode(bool first, bool direct, const PipeArgs& a, int blocks, hipStream_t s) {
     if (direct) hipLaunchKernelGGL((ort_shade_kernel<MODE, true, true>), dim3(blocks), dim3(kBlock), 0, s, a);
-    else if (first) hipLaunchKernelGGL((ort_shade_kernel<MODE, true, false>), dim3(blocks), dim3(kBlock), 0, s, a);
+    else if (first && a.out_format == ORT_FORMAT_RGB32F && a.out_place == ORT_PLACE_TILE &&
+             a.out_pitch == 12u * (unsigned)a.tm.tw)
+        hipLaunchKernelGGL((ort_shade_kernel<MODE, true, false>), dim3(blocks), dim3(kBlock), 0, s, a);
+    else if (first) hipLaunchKernelGGL((ort_shade_first_any<MODE>), dim3(blocks), dim3(kBlock), 0, s, a);
     else hipLaunchKernelGGL((ort_shade_kernel<MODE, false, false>), dim3(blocks), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
@@ -2409,8 +2488,24 @@ bool use_pixel_paths(const ort_ctx* ctx, int mode, int ns, int maxd) {
     return mode == 2 || ctx->n_nodes <= limit;
 }
 
+// Where the kernels write a frame (ort_output, checked and resolved by render_impl): data on the
+// device, the row pitch in bytes.
+struct DevOutput {
+    void* data;
+    long long pitch;
+    int format, place;
+};
+inline int format_bpp(int format) { return format == ORT_FORMAT_RGBA8 ? 4 : 12; }
+inline void set_output(PipeArgs& a, const DevOutput& o) {
+    a.out = o.data;
+    a.out_pitch = (unsigned)o.pitch;
+    a.out_format = o.format;
+    a.out_place = o.place;
+}
+
 // The frame as one ort_pixel_paths launch (use_pixel_paths); dout: the frame on the device.
-int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int mode, float* dout, hipStream_t s) {
+int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int mode, const DevOutput& dout,
+                       hipStream_t s) {
     const int tilesX = (t->width + 15) / 16, tilesY = (t->rows + 15) / 16;
     const long long blocks = (long long)tilesX * tilesY;
     PipeArgs a;
@@ -2422,7 +2517,7 @@ int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int
     a.tilesY = tilesY;
     a.total = (int)(blocks * kBlock);
     a.exact_only = ctx->exact_only || !ctx->ordered;
-    a.out = dout;
+    set_output(a, dout);
     // the cursor and done count: this frame's counter set (zero; the kernel's last workgroup
     // zeroes them again, so the set stays the pipeline's next one)
     if (!ctx->sync_ok) {
@@ -2621,10 +2716,52 @@ int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int
     return ORT_OK;
 }
 
-int render_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, float* out, int out_is_device,
-                void* stream, unsigned long long* dcounters) {
+// The frame's copy to a host output (the tight scratch frame; row by row where the caller gave a
+// pitch), or the wait of a synchronous device-output call.
+int finish_output(ort_ctx* ctx, const ort_output* o, const DevOutput& dout, const ort_tile* t, long long host_pitch,
+                  void* stream, hipStream_t s) {
+    if (!o->is_device) {
+        const size_t row_bytes = (size_t)t->width * (size_t)format_bpp(o->format);
+        if ((size_t)host_pitch == row_bytes)
+            HIPCHK(ctx, hipMemcpyAsync(o->data, dout.data, row_bytes * (size_t)t->rows, hipMemcpyDeviceToHost, s));
+        else
+            HIPCHK(ctx, hipMemcpy2DAsync(o->data, (size_t)host_pitch, dout.data, row_bytes, row_bytes, (size_t)t->rows,
+                                         hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+    } else if (!stream) {
+        HIPCHK(ctx, hipStreamSynchronize(s));
+    }
+    return ORT_OK;
+}
+
+// "" or what is wrong with the output description (every case before anything is launched).
+std::string check_output(const ort_params* p, const ort_tile* t, const ort_output* o) {
+    if (!o) return "null output";
+    if (o->format != ORT_FORMAT_RGB32F && o->format != ORT_FORMAT_RGBA8) return "output format: unknown ORT_FORMAT_*";
+    if (o->placement != ORT_PLACE_TILE && o->placement != ORT_PLACE_FRAME)
+        return "output placement: unknown ORT_PLACE_*";
+    if (o->reserved != 0) return "output reserved must be 0";
+    if (o->placement == ORT_PLACE_FRAME && !o->is_device)
+        return "output placement: ORT_PLACE_FRAME needs device output (is_device)";
+    const long long row_bytes =
+        (long long)(o->placement == ORT_PLACE_FRAME ? p->width : t->width) * format_bpp(o->format);
+    if (o->row_pitch_bytes % 4 != 0) return "output row_pitch_bytes must be a multiple of 4";
+    if (o->row_pitch_bytes > 0x7fffffffLL || row_bytes > 0x7fffffffLL)
+        return "output row_pitch_bytes: a row of at most 2^31 - 1 bytes";
+    if (o->row_pitch_bytes != 0 && o->row_pitch_bytes < row_bytes)
+        return "output row_pitch_bytes is below the row's " + std::to_string(row_bytes) + " bytes";
+    if (((uintptr_t)o->data & 3) != 0) return "output data must be 4-byte aligned";
+    return "";
+}
+
+int render_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, const ort_output* o, void* stream,
+                unsigned long long* dcounters) {
     const std::string bad = check_params(p, t);
     if (!bad.empty()) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_render: " + bad);
+    const std::string bad_out = check_output(p, t, o);
+    if (!bad_out.empty()) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_render: " + bad_out);
+    void* const out = o->data;
+    const int out_is_device = o->is_device;
     if (!ctx->has_scene) return fail(ctx, ORT_ERR_NO_SCENE, "ort_render: no scene uploaded");
     const int mode = (p->use_octree == 1) ? (ctx->layout == ORT_LAYOUT_COMPACT ? 0 : 1) : 2;
     if (mode != 2 && ctx->n_nodes <= 0) return fail(ctx, ORT_ERR_NO_SCENE, "ort_render: scene has no octree");
@@ -2645,23 +2782,22 @@ int render_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, float* out
     const size_t slots = (size_t)blocks * kBlock;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    float* dout = out;
+    // the rows' pitch: the caller's, or tight (tile rows, or the frame's under frame placement)
+    const long long tight =
+        (long long)(o->placement == ORT_PLACE_FRAME ? p->width : t->width) * format_bpp(o->format);
+    const long long pitch = o->row_pitch_bytes ? (long long)o->row_pitch_bytes : tight;
+    DevOutput dout = {out, pitch, o->format, o->placement};
     int rc;
-    if (!out_is_device) {
-        if ((rc = ensure(ctx, ctx->scratch_out, 12 * pix))) return rc;
-        dout = (float*)ctx->scratch_out.p;
+    if (!out_is_device) {  // a tight scratch frame on the device, copied out (finish_output)
+        if ((rc = ensure(ctx, ctx->scratch_out, (size_t)format_bpp(o->format) * pix))) return rc;
+        dout.data = ctx->scratch_out.p;
+        dout.pitch = tight;
     }
     const int ns = p->num_samples, maxd = p->max_depth;
     const bool direct = (ns == 1 && maxd == 1);
     if (!dcounters && use_pixel_paths(ctx, mode, ns, maxd)) {  // the frame in one launch
         if ((rc = ensure(ctx, ctx->defer_count, 128)) || (rc = render_pixel_paths(ctx, p, t, mode, dout, s))) return rc;
-        if (!out_is_device) {
-            HIPCHK(ctx, hipMemcpyAsync(out, dout, 12 * pix, hipMemcpyDeviceToHost, s));
-            HIPCHK(ctx, hipStreamSynchronize(s));
-        } else if (!stream) {
-            HIPCHK(ctx, hipStreamSynchronize(s));
-        }
-        return ORT_OK;
+        return finish_output(ctx, o, dout, t, pitch, stream, s);
     }
     if ((rc = ensure(ctx, ctx->hit, 8 * slots)) || (rc = ensure(ctx, ctx->defer_list, 4 * slots)) ||
         (rc = ensure(ctx, ctx->defer_count, 128)))
@@ -2753,7 +2889,7 @@ int render_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, float* out
     a.pc = (float4*)ctx->pc.p;
     a.prng = (float2*)ctx->prng.p;
     a.pcol = (float4*)ctx->pcol.p;
-    a.out = dout;
+    set_output(a, dout);
     a.counters = dcounters;
 #if ORT_ANALYSIS
     a.wclock = (ulonglong4*)ctx->wclock;
@@ -3074,13 +3210,7 @@ int render_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, float* out
     HIPCHK(ctx, hipEventRecord(ctx->ev1, s));
     ctx->timed = true;
     ctx->sync_ok = true;  // every launch enqueued: the counter sets are in step again
-    if (!out_is_device) {
-        HIPCHK(ctx, hipMemcpyAsync(out, dout, 12 * pix, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-    } else if (!stream) {
-        HIPCHK(ctx, hipStreamSynchronize(s));
-    }
-    return ORT_OK;
+    return finish_output(ctx, o, dout, t, pitch, stream, s);
 }
 
 }  // namespace
@@ -3392,8 +3522,14 @@ int ort_last_build_ms(const ort_ctx* ctx, float* ms) {
 
 int ort_render(ort_ctx* ctx, const ort_params* params, const ort_tile* tile, float* rgb_out, int out_is_device,
                void* stream) {
+    const ort_output o = {rgb_out, out_is_device, ORT_FORMAT_RGB32F, ORT_PLACE_TILE, 0, 0};
+    return ort_render_ex(ctx, params, tile, &o, stream);
+}
+
+int ort_render_ex(ort_ctx* ctx, const ort_params* params, const ort_tile* tile, const ort_output* output,
+                  void* stream) {
     if (!ctx) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_render: null ctx");
-    return render_impl(ctx, params, tile, rgb_out, out_is_device, stream, nullptr);
+    return render_impl(ctx, params, tile, output, stream, nullptr);
 }
 
 int ort_last_kernel_ms(ort_ctx* ctx, float* ms) {
@@ -3453,7 +3589,8 @@ int ort_count_traffic(ort_ctx* ctx, const ort_params* params, const ort_tile* ti
     const size_t pix = tile ? (size_t)tile->width * (size_t)tile->rows : 0;
     DevBuf tmp;
     if (pix) HIPCHK(ctx, hipMalloc(&tmp.p, 12 * pix));
-    const int rc = render_impl(ctx, params, tile, (float*)tmp.p, 1, nullptr, (unsigned long long*)ctx->counters.p);
+    const ort_output o = {tmp.p, 1, ORT_FORMAT_RGB32F, ORT_PLACE_TILE, 0, 0};
+    const int rc = render_impl(ctx, params, tile, &o, nullptr, (unsigned long long*)ctx->counters.p);
     if (rc == ORT_OK) {
         unsigned long long h[8] = {0};
         hipError_t e = hipMemcpy(h, ctx->counters.p, 64, hipMemcpyDeviceToHost);
@@ -3605,6 +3742,12 @@ int ort_debug_split_rays(const float* cr, int32_t n_spheres, const float* node_m
     } catch (const std::exception& ex) {
         return fail(nullptr, ORT_ERR_INTERNAL, ex.what());
     }
+}
+
+int ort_debug_pack_rgba8(const float* rgb, int64_t n_pixels, uint32_t* out) {
+    if (!rgb || !out || n_pixels < 0) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_pack_rgba8: null argument");
+    for (int64_t i = 0; i < n_pixels; ++i) out[i] = ort::pack_rgba8(ort::mk(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]));
+    return ORT_OK;
 }
 
 int ort_debug_fast_order(int32_t m, int32_t* order8, uint8_t* lut256) {

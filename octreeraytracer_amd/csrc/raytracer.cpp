@@ -130,6 +130,11 @@ ort_params Raytracer::frameParams(const Camera& cam) const {
 }
 
 int Raytracer::render(const Camera& cam, const ort_tile& tile, float* out, bool outIsDevice, void* stream) {
+    const ort_output o = {out, outIsDevice ? 1 : 0, ORT_FORMAT_RGB32F, ORT_PLACE_TILE, 0, 0};
+    return render(cam, tile, o, stream);
+}
+
+int Raytracer::render(const Camera& cam, const ort_tile& tile, const ort_output& output, void* stream) {
     if (!ctx && !group && !initialize()) return ORT_ERR_HIP;
     if (group) return ORT_ERR_UNSUPPORTED;  // a group renders whole frames (render(cam, rgb))
     if (!sceneReady) {
@@ -138,7 +143,7 @@ int Raytracer::render(const Camera& cam, const ort_tile& tile, float* out, bool 
         if (!sceneReady) return ORT_ERR_INVALID_ARG;
     }
     const ort_params p = frameParams(cam);
-    return ort_render(ctx, &p, &tile, out, outIsDevice ? 1 : 0, stream);
+    return ort_render_ex(ctx, &p, &tile, &output, stream);
 }
 
 int Raytracer::render(const Camera& cam, float* rgb) {

@@ -79,6 +79,9 @@ public:
     // stream-ordered on a caller hipStream_t.  Single-device configurations only (a group
     // renders whole frames: ORT_ERR_UNSUPPORTED).
     int render(const Camera& cam, const ort_tile& tile, float* out, bool outIsDevice, void* stream);
+    // The same with the output described by an ort_output (include/ort.h ort_render_ex): RGBA8
+    // as the GL default framebuffer holds it, a row pitch, the tile placed into a whole frame.
+    int render(const Camera& cam, const ort_tile& tile, const ort_output& output, void* stream);
 
     Camera camera;  // the reference keeps a global Camera (src/main.cpp:18); pose set like main()
     const RaytracerConfig& config() const { return cfg; }

@@ -1818,6 +1818,20 @@ ORT_FN V3 finish_pixel(V3 col, int ns) {
     return mk(ort_powf(col.x, g), ort_powf(col.y, g), ort_powf(col.z, g));
 }
 
+// One channel as the 8-bit default framebuffer holds it -- image.to_srgb8 in float32: NaN -> 0,
+// clamp to [0, 1], one multiply by 255, one add of 0.5 (two roundings, as numpy's), truncate.
+ORT_FN uint32_t quantise8(float x) {
+    if (!(x == x)) x = 0.0f;
+    x = x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x);
+    const float s = x * 255.0f;
+    return (uint32_t)(int)(s + 0.5f);
+}
+
+// The finished pixel as one RGBA8 word: memory bytes R, G, B, A with A = 255 (ORT_FORMAT_RGBA8).
+ORT_FN uint32_t pack_rgba8(V3 v) {
+    return quantise8(v.x) | quantise8(v.y) << 8 | quantise8(v.z) << 16 | 0xFF000000u;
+}
+
 // main() of the fragment shader (glsl:636-664) for pixel (px, py), py = 0 the bottom row,
 // as one sequential chain of the steps above (host emulation).
 // planes_b: the bounce walk's plane tables (trace_ray).

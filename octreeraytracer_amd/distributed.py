@@ -30,7 +30,8 @@ def rank_tile(width: int, height: int, rank: int, world: int, band: int = BAND) 
 
 
 def assemble(gathered, height: int, world: int, band: int = BAND, out=None):
-    """gathered: [world, per*band, W, 3] (torch tensor or numpy array) -> [height, W, 3].
+    """gathered: [world, per*band, W, C] (torch tensor or numpy array) -> [height, W, C], in
+    the dtype given: C = 3 float32 frames and C = 4 uint8 (RGBA8) frames alike.
     Global band b*world + r is band b of rank r."""
     if world == 1:
         frame = gathered[0][:height]
@@ -39,11 +40,11 @@ def assemble(gathered, height: int, world: int, band: int = BAND, out=None):
             return out
         return frame
     per = gathered.shape[1] // band
-    W = gathered.shape[2]
+    W, ch = gathered.shape[2], gathered.shape[3]
     if hasattr(gathered, "permute"):
-        g = gathered.reshape(world, per, band, W, 3).permute(1, 0, 2, 3, 4).reshape(per * world * band, W, 3)
+        g = gathered.reshape(world, per, band, W, ch).permute(1, 0, 2, 3, 4).reshape(per * world * band, W, ch)
     else:
-        g = gathered.reshape(world, per, band, W, 3).transpose(1, 0, 2, 3, 4).reshape(per * world * band, W, 3)
+        g = gathered.reshape(world, per, band, W, ch).transpose(1, 0, 2, 3, 4).reshape(per * world * band, W, ch)
     if out is not None:
         if hasattr(out, "copy_"):
             out.copy_(g[:height])
@@ -72,8 +73,9 @@ class FrameGather:
     before finish() of that submission (bench.py double-buffers its tiles)."""
 
     def __init__(self, dist, width: int, height: int, world: int, rank: int, device, band: int = BAND,
-                 depth: int = 1, timeout_s: float | None = None):
-        """timeout_s: bound of finish()'s wait for a gather (None: the process group's own); on
+                 depth: int = 1, timeout_s: float | None = None, channels: int = 3, dtype=None):
+        """channels, dtype: the band tiles' trailing size and torch dtype (None: float32) -- 4 and
+        torch.uint8 for frames rendered with format="rgba8".  timeout_s: bound of finish()'s wait for a gather (None: the process group's own); on
         expiry finish() raises GatherTimeout naming the rank and the slot.  (With the nccl
         backend an async gather's wait only orders the streams: a stalled RCCL gather is
         bounded by the process group's timeout, init_process_group(timeout=...), whose
@@ -82,10 +84,11 @@ class FrameGather:
         self.dist, self.world, self.rank, self.height, self.band = dist, world, rank, height, band
         self.timeout_s = timeout_s
         rows = rank_tile(width, height, rank, world, band).rows
-        self.slots = [torch.empty((world, rows, width, 3), dtype=torch.float32, device=device)
+        dtype = torch.float32 if dtype is None else dtype
+        self.slots = [torch.empty((world, rows, width, channels), dtype=dtype, device=device)
                       for _ in range(depth)] if rank == 0 and world > 1 else None
         self.gathered = self.slots[0] if self.slots else None
-        self.frame = torch.empty((height, width, 3), dtype=torch.float32, device=device) if rank == 0 else None
+        self.frame = torch.empty((height, width, channels), dtype=dtype, device=device) if rank == 0 else None
 
     def __call__(self, local):
         if self.world == 1:

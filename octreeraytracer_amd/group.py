@@ -81,41 +81,47 @@ class RenderGroup:
                                                      L.fptr(t[0]), L.fptr(t[1]), L.iptr(t[2]), L.iptr(t[3]),
                                                      L.iptr(t[4]), tree.n_nodes, L.iptr(t[5]), tree.n_indices))
 
-    def _out(self, params: FrameParams, out):
-        n = params.height * params.width * 3
+    def _out(self, params: FrameParams, out, format: str = "rgb32f"):
+        if format not in L.FORMATS:
+            raise ValueError(f"render: format must be one of {sorted(L.FORMATS)} (got {format!r})")
+        fmt = L.FORMATS[format]
+        ch, np_dtype = (3, np.float32) if fmt == L.ORT_FORMAT_RGB32F else (4, np.uint8)
+        n = params.height * params.width * ch
         if out is None:
-            out = np.empty((params.height, params.width, 3), np.float32)
+            out = np.empty((params.height, params.width, ch), np_dtype)
         if isinstance(out, np.ndarray):
-            if out.dtype != np.float32 or not out.flags.c_contiguous or out.size < n:
-                raise ValueError("render: out must be a contiguous float32 array of H*W*3 elements")
-            return out, out.ctypes.data_as(C.c_void_p), 0
+            if out.dtype != np_dtype or not out.flags.c_contiguous or out.size < n:
+                raise ValueError(f"render: out must be a contiguous {np.dtype(np_dtype).name} array of H*W*{ch} elements")
+            return out, out.ctypes.data_as(C.c_void_p), 0, fmt
         import torch
-        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n:
-            raise ValueError("render: out must be a contiguous float32 tensor of H*W*3 elements")
+        t_dtype = torch.float32 if fmt == L.ORT_FORMAT_RGB32F else torch.uint8
+        if out.dtype != t_dtype or not out.is_contiguous() or out.numel() < n:
+            raise ValueError(f"render: out must be a contiguous {t_dtype} tensor of H*W*{ch} elements")
         if out.device.type != "cuda" or out.device.index != self.devices[0]:
             raise ValueError(f"render: out is on {out.device}, the group assembles on cuda:{self.devices[0]}")
-        return out, C.c_void_p(out.data_ptr()), 1
+        return out, C.c_void_p(out.data_ptr()), 1, fmt
 
-    def render(self, params: FrameParams, out=None):
+    def render(self, params: FrameParams, out=None, format: str = "rgb32f"):
         """Full frame: a new (H, W, 3) float32 numpy array, a numpy array, or a float32 torch
-        tensor on devices[0] (device output).  Synchronous."""
+        tensor on devices[0] (device output).  Synchronous.  format="rgba8": (H, W, 4) uint8,
+        the ranks' bands rendered, exchanged and assembled at 4 bytes per pixel."""
         p = params.to_c()
-        out, ptr, dev = self._out(params, out)
-        self._check(self._lib.ort_group_render(self._g, C.byref(p), ptr, dev))
+        out, ptr, dev, fmt = self._out(params, out, format)
+        self._check(self._lib.ort_group_render_fmt(self._g, C.byref(p), ptr, dev, fmt))
         return out
 
-    def submit(self, params: FrameParams, out) -> int:
-        """Enqueue a frame into `out` -- a numpy array or a float32 torch tensor on devices[0],
-        required: the frame is written asynchronously -- and return its ticket at once
-        (ort_group_submit).  Keep `out` untouched until wait(ticket); the group holds a
-        reference to it until then."""
+    def submit(self, params: FrameParams, out, format: str = "rgb32f") -> int:
+        """Enqueue a frame into `out` -- a numpy array or a float32 torch tensor on devices[0]
+        (uint8 with format="rgba8"), required: the frame is written asynchronously -- and return
+        its ticket at once (ort_group_submit_fmt).  Keep `out` untouched until wait(ticket); the
+        group holds a reference to it until then."""
         if out is None:
             raise ValueError("submit: out is required (the frame is written after submit returns; read it "
                              "after wait(ticket))")
         p = params.to_c()
-        out, ptr, dev = self._out(params, out)
+        out, ptr, dev, fmt = self._out(params, out, format)
         tk = C.c_int64(-1)
-        self._check(self._lib.ort_group_submit(self._g, C.byref(p), ptr, dev, C.byref(tk)))
+        self._check(self._lib.ort_group_submit_fmt(self._g, C.byref(p), ptr, dev, fmt, C.byref(tk)))
         self._pending[tk.value] = out
         # submitting frame k waited for the frame that last used its slot (k - inflight) and
         # every frame before it on that slot: those outputs are complete

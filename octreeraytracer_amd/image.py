@@ -14,7 +14,12 @@ import numpy as np
 
 def to_srgb8(rgb: np.ndarray) -> np.ndarray:
     """Quantise the shader's output (already gamma-corrected, glsl:661) to 8 bits, as the
-    default framebuffer would (clamp to [0,1], round)."""
+    default framebuffer would (clamp to [0,1], round).  A uint8 frame (rendered with
+    format="rgba8": the kernel has quantised it the same way) passes through, without its
+    alpha channel."""
+    rgb = np.asarray(rgb)
+    if rgb.dtype == np.uint8:
+        return rgb[..., :3]
     return (np.clip(np.nan_to_num(rgb, nan=0.0), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
 
 

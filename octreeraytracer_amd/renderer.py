@@ -266,32 +266,66 @@ class Renderer:
                 "tree_depth": i.tree_depth, "device_bytes": i.device_bytes}
 
     # -- frames ----------------------------------------------------------------------
-    def render(self, params: FrameParams, tile: Tile | None = None, out=None, stream=None):
+    def render(self, params: FrameParams, tile: Tile | None = None, out=None, stream=None, *,
+               format: str = "rgb32f", row_pitch: int | None = None, place: str = "tile"):
         """Render a tile.  out: None (returns a new (rows, width, 3) float32 numpy array),
         a numpy array, or a device pointer (int) / torch CUDA tensor on this device.
         stream: None (synchronous) or a hipStream_t handle (int), e.g.
         torch.cuda.Stream().cuda_stream.  The null stream (handle 0, torch's default
-        stream) cannot be told apart from "no stream": it renders synchronously."""
+        stream) cannot be told apart from "no stream": it renders synchronously.
+
+        format: "rgb32f" (3 float32 per pixel) or "rgba8" (4 uint8: R, G, B, A = 255, each
+        channel ``image.to_srgb8`` of the float pixel, quantised by the kernel; out=None then
+        returns a (rows, width, 4) uint8 array).  row_pitch: bytes from one output row to the
+        next (a multiple of 4, at least the row's bytes; None: tight); the bytes between rows
+        are left untouched.  place: "tile" (output row j is tile row j) or "frame" (out is a
+        whole width x height frame on the device, the pixel (x, y) lands at row y, column x, and
+        band padding rows are not written): ort_render_ex (include/ort.h)."""
         tile = tile or Tile.full(params)
         p, t = params.to_c(), tile.to_c()
         s = C.c_void_p(int(stream)) if stream else None
+        if format not in L.FORMATS:
+            raise ValueError(f"render: format must be one of {sorted(L.FORMATS)} (got {format!r})")
+        if place not in L.PLACEMENTS:
+            raise ValueError(f"render: place must be one of {sorted(L.PLACEMENTS)} (got {place!r})")
+        fmt, plc = L.FORMATS[format], L.PLACEMENTS[place]
+        bpp = L.FORMAT_BPP[fmt]
+        np_dtype, channels = (np.float32, 3) if fmt == L.ORT_FORMAT_RGB32F else (np.uint8, 4)
+        # the bytes the description covers: rows of row_bytes, pitch apart
+        row_bytes = (params.width if plc == L.ORT_PLACE_FRAME else tile.width) * bpp
+        n_rows = params.height if plc == L.ORT_PLACE_FRAME else tile.rows
+        pitch = row_bytes if row_pitch is None else int(row_pitch)
+        if pitch % 4 != 0:
+            raise ValueError(f"render: row_pitch must be a multiple of 4 (got {pitch})")
+        if pitch < row_bytes:
+            raise ValueError(f"render: row_pitch {pitch} is below the row's {row_bytes} bytes")
+        need = (n_rows - 1) * pitch + row_bytes if n_rows > 0 else 0
         if out is None:
-            out = np.empty((tile.rows, tile.width, 3), np.float32)
+            if plc == L.ORT_PLACE_FRAME or row_pitch is not None:
+                raise ValueError("render: place='frame' and row_pitch describe a caller's buffer: pass out")
+            out = np.empty((tile.rows, tile.width, channels), np_dtype)
+        o = L.OrtOutput(None, 0, fmt, plc, 0, 0 if row_pitch is None else pitch)
         if isinstance(out, np.ndarray):
-            if out.dtype != np.float32 or not out.flags.c_contiguous or out.size < tile.rows * tile.width * 3:
-                raise ValueError(f"render: out must be a C-contiguous float32 array of >= {tile.rows * tile.width * 3} "
-                                 f"elements (got {out.dtype}, {out.size}, contiguous={out.flags.c_contiguous})")
-            self._check(self._lib.ort_render(self._ctx, C.byref(p), C.byref(t), out.ctypes.data_as(C.c_void_p), 0, s))
+            if plc == L.ORT_PLACE_FRAME:
+                raise ValueError("render: place='frame' writes device memory: out must be a device pointer or tensor")
+            if out.dtype != np_dtype or not out.flags.c_contiguous or out.nbytes < need:
+                raise ValueError(f"render: out must be a C-contiguous {np.dtype(np_dtype).name} array of >= {need} "
+                                 f"bytes (got {out.dtype}, {out.nbytes} bytes, contiguous={out.flags.c_contiguous})")
+            o.data = out.ctypes.data_as(C.c_void_p)
+            self._check(self._lib.ort_render_ex(self._ctx, C.byref(p), C.byref(t), C.byref(o), s))
             return out
         ptr = out.data_ptr() if hasattr(out, "data_ptr") else int(out)
-        if hasattr(out, "numel"):  # a torch tensor: float32, contiguous, on this context's GPU
+        if hasattr(out, "numel"):  # a torch tensor: the format's dtype, contiguous, on this context's GPU
             import torch
-            if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < tile.rows * tile.width * 3:
-                raise ValueError(f"render: out must be a contiguous float32 tensor of >= {tile.rows * tile.width * 3} "
-                                 f"elements (got {out.dtype}, {out.numel()}, contiguous={out.is_contiguous()})")
+            t_dtype = torch.float32 if fmt == L.ORT_FORMAT_RGB32F else torch.uint8
+            nbytes = out.numel() * out.element_size()
+            if out.dtype != t_dtype or not out.is_contiguous() or nbytes < need:
+                raise ValueError(f"render: out must be a contiguous {t_dtype} tensor of >= {need} bytes "
+                                 f"(got {out.dtype}, {nbytes} bytes, contiguous={out.is_contiguous()})")
             if out.device.type != "cuda" or out.device.index != self.device:
                 raise ValueError(f"render: out is on {out.device}, the context renders on cuda:{self.device}")
-        self._check(self._lib.ort_render(self._ctx, C.byref(p), C.byref(t), C.c_void_p(ptr), 1, s))
+        o.data, o.is_device = C.c_void_p(ptr), 1
+        self._check(self._lib.ort_render_ex(self._ctx, C.byref(p), C.byref(t), C.byref(o), s))
         return out
 
     def last_kernel_ms(self) -> float:
