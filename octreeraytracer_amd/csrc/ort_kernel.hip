@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <type_traits>
 #include <cstring>
 #include <new>
@@ -2034,10 +2035,17 @@ void free_buf(DevBuf& b) {
     b.bytes = 0;
 }
 
+// The scene's device buffers (C: ort_ctx or const ort_ctx): the one list free_scene frees and
+// ort_scene_get_info sums.
+template <class C, class F>
+void each_scene_buffer(C& c, F f) {
+    for (auto* b : {&c.sph_cr, &c.sph_ma, &c.sph_fr, &c.node, &c.kid, &c.nk, &c.leaf_sph, &c.leaf_idx, &c.planes,
+                    &c.lds_img, &c.lds_rev, &c.nodeA, &c.nodeB, &c.cnt, &c.indices})
+        f(*b);
+}
+
 void free_scene(ort_ctx* c) {
-    DevBuf* all[] = {&c->sph_cr, &c->sph_ma, &c->sph_fr, &c->node, &c->kid, &c->nk, &c->leaf_sph, &c->leaf_idx,
-                     &c->planes, &c->lds_img, &c->lds_rev, &c->nodeA, &c->nodeB, &c->cnt, &c->indices};
-    for (DevBuf* b : all) free_buf(*b);
+    each_scene_buffer(*c, [](DevBuf& b) { free_buf(b); });
     ort::freeGpuTree(c->tree);
     c->has_scene = false;
 }
@@ -2323,81 +2331,137 @@ int ensure(ort_ctx* ctx, DevBuf& b, size_t bytes) {
     return ORT_OK;
 }
 
-template <bool COUNT, bool PRIMARY>
-hipError_t launch_trace_p(int mode, const PipeArgs& a, int blocks, int pblocks, size_t lds, hipStream_t s, int fuse) {
-    if (PRIMARY && mode == 0 && a.pair && pblocks == 0) {  // tile pairs: blocks = workgroups (one per pair)
-        const dim3 g(blocks), t(kBlock);
-        if (a.S.depth > 8) {
-            if (fuse == 1) hipLaunchKernelGGL((ort_trace_pair_deep<COUNT, 1>), g, t, lds, s, a);
-            else if (fuse == 2) hipLaunchKernelGGL((ort_trace_pair_deep<COUNT, 2>), g, t, lds, s, a);
-            else hipLaunchKernelGGL((ort_trace_pair_deep<COUNT, 0>), g, t, lds, s, a);
-        } else {
-            if (fuse == 1) hipLaunchKernelGGL((ort_trace_pair<COUNT, 1>), g, t, lds, s, a);
-            else if (fuse == 2) hipLaunchKernelGGL((ort_trace_pair<COUNT, 2>), g, t, lds, s, a);
-            else hipLaunchKernelGGL((ort_trace_pair<COUNT, 0>), g, t, lds, s, a);
-        }
-        return hipGetLastError();
-    }
-    if (mode == 0 && pblocks > 0) {
-        if (a.S.depth > 8)
-            hipLaunchKernelGGL((ort_trace_persistent<COUNT, true>), dim3(pblocks), dim3(kPersistDeepBlock),
-                               lds_bytes(0, a.S.depth, false, kRevBounce, kPersistDeepBlock), s, a);
-        else hipLaunchKernelGGL((ort_trace_persistent<COUNT, false>), dim3(pblocks), dim3(kBlock), lds, s, a);
-    }
-    else if (mode == 0 && a.S.depth > 8)
-    {
-        if (fuse == 1) hipLaunchKernelGGL((ort_trace_compact_deep<COUNT, PRIMARY, 1>), dim3(blocks), dim3(kBlock), lds, s, a);
-        else if (fuse == 2) hipLaunchKernelGGL((ort_trace_compact_deep<COUNT, PRIMARY, 2>), dim3(blocks), dim3(kBlock), lds, s, a);
-        else hipLaunchKernelGGL((ort_trace_compact_deep<COUNT, PRIMARY, 0>), dim3(blocks), dim3(kBlock), lds, s, a);
-    }
-    else if (mode == 0 && fuse == 1)
-        hipLaunchKernelGGL((ort_trace_compact<COUNT, PRIMARY, 1>), dim3(blocks), dim3(kBlock), lds, s, a);
-    else if (mode == 0 && fuse == 2)
-        hipLaunchKernelGGL((ort_trace_compact<COUNT, PRIMARY, 2>), dim3(blocks), dim3(kBlock), lds, s, a);
-    else if (mode == 0) hipLaunchKernelGGL((ort_trace_compact<COUNT, PRIMARY, 0>), dim3(blocks), dim3(kBlock), lds, s, a);
-    else if (mode == 1) hipLaunchKernelGGL((ort_trace_kernel<1, COUNT, PRIMARY>), dim3(blocks), dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL((ort_trace_kernel<2, COUNT, PRIMARY>), dim3(blocks), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
+// The dispatchers below stand in the order of their kernels in the code object (a kernel template
+// is emitted where it is first named): moving one reorders the device code.
+// A runtime int as a template argument: f(std::integral_constant<int, V>) for the first listed V
+// equal to v, the LAST listed one when none is.  Every dispatcher below lists exactly the
+// combinations it compiles: a kernel instance exists only where one of them names it.
+template <int V, int... Rest, class F>
+inline auto pick(int v, F&& f) {
+    if constexpr (sizeof...(Rest) == 0) return f(std::integral_constant<int, V>{});
+    else return v == V ? f(std::integral_constant<int, V>{}) : pick<Rest...>(v, f);
 }
+#define ORT_V(x) decltype(x)::value  // the constant a pick() lambda was handed
 
-template <bool COUNT>
-hipError_t launch_trace(int mode, bool primary, const PipeArgs& a, int blocks, int pblocks, size_t lds, hipStream_t s,
-                        int fuse) {
-    return primary ? launch_trace_p<COUNT, true>(mode, a, blocks, pblocks, lds, s, fuse)
-                   : launch_trace_p<COUNT, false>(mode, a, blocks, pblocks, lds, s, 0);
-}
-
-template <int MODE>
-hipError_t launch_shade_mode(bool first, bool direct, const PipeArgs& a, int blocks, hipStream_t s) {
-    if (direct) hipLaunchKernelGGL((ort_shade_kernel<MODE, true, true>), dim3(blocks), dim3(kBlock), 0, s, a);
-    else if (first && a.out_format == ORT_FORMAT_RGB32F && a.out_place == ORT_PLACE_TILE &&
-             a.out_pitch == 12u * (unsigned)a.tm.tw)
-        hipLaunchKernelGGL((ort_shade_kernel<MODE, true, false>), dim3(blocks), dim3(kBlock), 0, s, a);
-    else if (first) hipLaunchKernelGGL((ort_shade_first_any<MODE>), dim3(blocks), dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL((ort_shade_kernel<MODE, false, false>), dim3(blocks), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-
+// The shade kernel of a bounce: DIRECT, bounce 0 into a tight float tile (ort_render's own output),
+// bounce 0 into any other output, a later bounce.
 hipError_t launch_shade(int mode, bool first, bool direct, const PipeArgs& a, int blocks, hipStream_t s) {
-    if (mode == 0) return launch_shade_mode<0>(first, direct, a, blocks, s);
-    if (mode == 1) return launch_shade_mode<1>(first, direct, a, blocks, s);
-    return launch_shade_mode<2>(first, direct, a, blocks, s);
+    const dim3 g(blocks), t(kBlock);
+    const bool tight_f32 = a.out_format == ORT_FORMAT_RGB32F && a.out_place == ORT_PLACE_TILE &&
+                           a.out_pitch == 12u * (unsigned)a.tm.tw;
+    pick<0, 1, 2>(mode, [&](auto MODE) {
+        if (direct) hipLaunchKernelGGL((ort_shade_kernel<ORT_V(MODE), true, true>), g, t, 0, s, a);
+        else if (first && tight_f32) hipLaunchKernelGGL((ort_shade_kernel<ORT_V(MODE), true, false>), g, t, 0, s, a);
+        else if (first) hipLaunchKernelGGL((ort_shade_first_any<ORT_V(MODE)>), g, t, 0, s, a);
+        else hipLaunchKernelGGL((ort_shade_kernel<ORT_V(MODE), false, false>), g, t, 0, s, a);
+    });
+    return hipGetLastError();
 }
 
-// Resident workgroups of the persistent trace kernel (a plain launch: extra groups just
-// start when others finish; no grid-wide synchronisation depends on residency).
-int persistent_blocks(int device, bool count, bool deep, int depth, size_t lds, long long needed) {
+// Resident workgroups of a persistent grid (a plain launch: extra groups just start when others
+// finish; no grid-wide synchronisation depends on residency), at most `needed`.
+template <class K>
+int resident_blocks(int device, K kernel, int threads, size_t lds, long long needed) {
     int per_cu = 0, cus = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    const size_t dlds = lds_bytes(0, depth, false, kRevBounce, kPersistDeepBlock);
-    if (count)
-        (void)(deep ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ort_trace_persistent<true, true>, kPersistDeepBlock, dlds)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ort_trace_persistent<true, false>, kBlock, lds));
-    else
-        (void)(deep ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ort_trace_persistent<false, true>, kPersistDeepBlock, dlds)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ort_trace_persistent<false, false>, kBlock, lds));
-    long long b = (long long)std::max(per_cu, 1) * std::max(cus, 1);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds);
+    const long long b = (long long)std::max(per_cu, 1) * std::max(cus, 1);
     return (int)std::max(1LL, std::min(b, needed));
+}
+
+// ... of the persistent trace kernel
+int persistent_blocks(int device, bool count, bool deep, int depth, size_t lds, long long needed) {
+    const size_t dlds = lds_bytes(0, depth, false, kRevBounce, kPersistDeepBlock);
+    return pick<1, 0>(count, [&](auto COUNT) {
+        return deep ? resident_blocks(device, ort_trace_persistent<ORT_V(COUNT), true>, kPersistDeepBlock, dlds, needed)
+                    : resident_blocks(device, ort_trace_persistent<ORT_V(COUNT), false>, kBlock, lds, needed);
+    });
+}
+
+// One ort_pixel_paths launch (pm: 0 whole chains, 1 the samples' chunks in parallel, 2 recording or
+// fixup; the variant of the scene's walk: brute force, a deep tree, an LDS-resident scene, or the
+// plain compact walk) over a persistent grid sized by the variant's occupancy, at most `needed`
+// workgroups.
+hipError_t launch_pixel_paths(int pm, int device, int mode, bool deep, bool lds_scene, size_t lds, long long needed,
+                              const PipeArgs& a, hipStream_t s) {
+    const int variant = mode == 2 ? 0 : (deep ? 1 : (lds_scene ? 2 : 3));
+    pick<2, 0, 1>(pm, [&](auto PM) {
+        pick<0, 1, 2, 3>(variant, [&](auto V) {
+            constexpr int MODE = ORT_V(V) == 0 ? 2 : 0;
+            constexpr bool DEEP = ORT_V(V) == 1, LDS = ORT_V(V) == 2;
+            const int g = resident_blocks(device, ort_pixel_paths<MODE, DEEP, LDS, ORT_V(PM)>, kBlock, lds, needed);
+            hipLaunchKernelGGL((ort_pixel_paths<MODE, DEEP, LDS, ORT_V(PM)>), dim3(g), dim3(kBlock), lds, s, a);
+        });
+    });
+    return hipGetLastError();
+}
+
+// The split walks of the listed heavy camera rays (FUSE 1: one bounce, shading fused; 2: bounce
+// 0 of a longer path).
+#ifndef ORT_SPLIT_BLOCKS
+#define ORT_SPLIT_BLOCKS 32  // 1024 heavy rays in flight; more loop
+#endif
+hipError_t launch_trace_split(bool deep, int fmode, const PipeArgs& a, size_t lds, hipStream_t s) {
+    pick<1, 0>(deep, [&](auto DEEP) {
+        pick<1, 2>(fmode, [&](auto FUSE) {
+            hipLaunchKernelGGL((ort_trace_split<ORT_V(DEEP) != 0, ORT_V(FUSE)>), dim3(ORT_SPLIT_BLOCKS), dim3(kBlock), lds, s, a);
+        });
+    });
+    return hipGetLastError();
+}
+
+// The trace launch of a bounce: tile pairs, the persistent kernel over a list, the per-tile
+// kernels of the compact layout, or the explicit-layout / brute-force kernel.
+template <bool COUNT, bool PRIMARY>
+hipError_t launch_trace_p(int mode, const PipeArgs& a, int blocks, int pblocks, size_t lds, hipStream_t s, int fuse) {
+    const dim3 g(blocks), t(kBlock);
+    const int deep = a.S.depth > 8;
+    if (PRIMARY && mode == 0 && a.pair && pblocks == 0)  // tile pairs: blocks = workgroups (one per pair)
+        pick<1, 0>(deep, [&](auto DEEP) {
+            pick<1, 2, 0>(fuse, [&](auto FUSE) {
+                if constexpr (ORT_V(DEEP)) hipLaunchKernelGGL((ort_trace_pair_deep<COUNT, ORT_V(FUSE)>), g, t, lds, s, a);
+                else hipLaunchKernelGGL((ort_trace_pair<COUNT, ORT_V(FUSE)>), g, t, lds, s, a);
+            });
+        });
+    else if (mode == 0 && pblocks > 0 && deep)
+        hipLaunchKernelGGL((ort_trace_persistent<COUNT, true>), dim3(pblocks), dim3(kPersistDeepBlock),
+                           lds_bytes(0, a.S.depth, false, kRevBounce, kPersistDeepBlock), s, a);
+    else if (mode == 0 && pblocks > 0)
+        hipLaunchKernelGGL((ort_trace_persistent<COUNT, false>), dim3(pblocks), t, lds, s, a);
+    else if (mode == 0)
+        pick<1, 0>(deep, [&](auto DEEP) {
+            pick<1, 2, 0>(fuse, [&](auto FUSE) {
+                if constexpr (ORT_V(DEEP)) hipLaunchKernelGGL((ort_trace_compact_deep<COUNT, PRIMARY, ORT_V(FUSE)>), g, t, lds, s, a);
+                else hipLaunchKernelGGL((ort_trace_compact<COUNT, PRIMARY, ORT_V(FUSE)>), g, t, lds, s, a);
+            });
+        });
+    else
+        pick<1, 2>(mode, [&](auto MODE) { hipLaunchKernelGGL((ort_trace_kernel<ORT_V(MODE), COUNT, PRIMARY>), g, t, 0, s, a); });
+    return hipGetLastError();
+}
+
+hipError_t launch_trace(bool count, int mode, bool primary, const PipeArgs& a, int blocks, int pblocks, size_t lds,
+                        hipStream_t s, int fuse) {
+    return pick<1, 0>(count, [&](auto COUNT) {
+        return primary ? launch_trace_p<ORT_V(COUNT) != 0, true>(mode, a, blocks, pblocks, lds, s, fuse)
+                       : launch_trace_p<ORT_V(COUNT) != 0, false>(mode, a, blocks, pblocks, lds, s, 0);
+    });
+}
+
+// The exact walk of the deferred rays: a grid-stride loop over the (usually no) deferred rays; a
+// small grid dispatches fast.  Seven instances: counting renders never fuse bounce 0 of a longer
+// path (fmode 2), and only camera rays fuse at all.
+hipError_t launch_trace_exact(bool count, bool prim, int fmode, const PipeArgs& a, size_t lds, hipStream_t s) {
+    const dim3 g(256), t(kBlock);
+    pick<1, 0>(count, [&](auto COUNT) {
+        constexpr bool C = ORT_V(COUNT) != 0;
+        if (fmode == 1) hipLaunchKernelGGL((ort_trace_exact<C, true, 1>), g, t, lds, s, a);
+        else if (!C && fmode == 2) {
+            if constexpr (!C) hipLaunchKernelGGL((ort_trace_exact<false, true, 2>), g, t, lds, s, a);
+        } else if (prim) hipLaunchKernelGGL((ort_trace_exact<C, true, 0>), g, t, lds, s, a);
+        else hipLaunchKernelGGL((ort_trace_exact<C, false, 0>), g, t, lds, s, a);
+    });
+    return hipGetLastError();
 }
 
 // Whole-pixel paths (ort_pixel_paths): the frame in one launch.  Auto (ORT_OPT_PIXEL_PATHS -1):
@@ -2437,35 +2501,6 @@ constexpr long long kSpecAutoPixels = 1 << 20;  // ... and without timing events
 inline size_t spec_bytes(size_t slots, int ns) { return slots * ((size_t)spec_nch(ns) * 16 + (size_t)ns * 12 + 28); }
 bool use_pixel_paths(const ort_ctx* ctx, int mode, int ns, int maxd);
 
-template <int MODE, bool DEEP, bool LDS, int PM>
-int pixel_paths_blocks(int device, size_t lds, long long needed) {
-    int per_cu = 0, cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ort_pixel_paths<MODE, DEEP, LDS, PM>, kBlock, lds);
-    const long long b = (long long)std::max(per_cu, 1) * std::max(cus, 1);
-    return (int)std::max(1LL, std::min(b, needed));
-}
-
-// One ort_pixel_paths launch (the variant of the scene's walk) over a persistent grid sized by
-// the variant's occupancy, at most `needed` workgroups.
-template <int PM>
-hipError_t launch_pixel_paths(const ort_ctx* ctx, int mode, bool deep, bool lds_scene, size_t lds, long long needed,
-                              const PipeArgs& a, hipStream_t s) {
-    if (mode == 2) {
-        const int g = pixel_paths_blocks<2, false, false, PM>(ctx->device, 0, needed);
-        hipLaunchKernelGGL((ort_pixel_paths<2, false, false, PM>), dim3(g), dim3(kBlock), 0, s, a);
-    } else if (deep) {
-        const int g = pixel_paths_blocks<0, true, false, PM>(ctx->device, lds, needed);
-        hipLaunchKernelGGL((ort_pixel_paths<0, true, false, PM>), dim3(g), dim3(kBlock), lds, s, a);
-    } else if (lds_scene) {
-        const int g = pixel_paths_blocks<0, false, true, PM>(ctx->device, lds, needed);
-        hipLaunchKernelGGL((ort_pixel_paths<0, false, true, PM>), dim3(g), dim3(kBlock), lds, s, a);
-    } else {
-        const int g = pixel_paths_blocks<0, false, false, PM>(ctx->device, lds, needed);
-        hipLaunchKernelGGL((ort_pixel_paths<0, false, false, PM>), dim3(g), dim3(kBlock), lds, s, a);
-    }
-    return hipGetLastError();
-}
 
 // FNV-1a of the frame shape and scene: the previous-frame hints (list lengths, walk costs)
 // belong to one of these
@@ -2503,11 +2538,9 @@ inline void set_output(PipeArgs& a, const DevOutput& o) {
     a.out_place = o.place;
 }
 
-// The frame as one ort_pixel_paths launch (use_pixel_paths); dout: the frame on the device.
-int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int mode, const DevOutput& dout,
-                       hipStream_t s) {
-    const int tilesX = (t->width + 15) / 16, tilesY = (t->rows + 15) / 16;
-    const long long blocks = (long long)tilesX * tilesY;
+// The argument block's part that both render paths fill alike: camera, scene, tile, grid, output.
+PipeArgs base_args(const ort_ctx* ctx, const ort_params* p, const ort_tile* t, const DevOutput& o, int tilesX,
+                   int tilesY, long long blocks) {
     PipeArgs a;
     std::memset(&a, 0, sizeof(a));
     a.pp = pixel_params(p);
@@ -2517,21 +2550,41 @@ int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int
     a.tilesY = tilesY;
     a.total = (int)(blocks * kBlock);
     a.exact_only = ctx->exact_only || !ctx->ordered;
-    set_output(a, dout);
-    // the cursor and done count: this frame's counter set (zero; the kernel's last workgroup
-    // zeroes them again, so the set stays the pipeline's next one)
-    if (!ctx->sync_ok) {
-        HIPCHK(ctx, hipMemsetAsync(ctx->defer_count.p, 0, 128, s));
-        ctx->sync_set = 0;
-        ctx->pre_ok = false;
-        ctx->pp_sig = 0;  // (the class lists' counts re-zeroed below)
-    }
-    ctx->sync_ok = false;
-    a.sync = (int*)ctx->defer_count.p + 16 * ctx->sync_set;
+    set_output(a, o);
 #if ORT_ANALYSIS
-    a.wclock = (ulonglong4*)ctx->wclock;  // ORT_PIXEL_CLOCK builds (tools/pixel_clock.py)
+    a.wclock = (ulonglong4*)ctx->wclock;  // ORT_PERSIST_CLOCK / ORT_PIXEL_CLOCK builds (tools/*_clock.py)
     a.wclock_n = (int)ctx->wclock_n;
 #endif
+    return a;
+}
+
+// Two sets of 16 counters (deferred count, persistent cursor, heavy list) in defer_count: a launch
+// uses one and its exact kernel (or ort_pixel_paths' last workgroup) zeroes the other for the next
+// launch; a memset re-zeroes both after a failed render or a new buffer (sync_ok).  fresh: it did.
+int begin_counter_sets(ort_ctx* ctx, hipStream_t s, bool& fresh) {
+    fresh = !ctx->sync_ok;
+    if (fresh) {
+        HIPCHK(ctx, hipMemsetAsync(ctx->defer_count.p, 0, 128, s));
+        ctx->sync_set = 0;
+        ctx->pre_ok = false;  // a failed render may not have listed the next frame's heavy rays
+    }
+    ctx->sync_ok = false;  // until this render has enqueued all its launches
+    return ORT_OK;
+}
+
+// The frame as one ort_pixel_paths launch (use_pixel_paths); dout: the frame on the device.
+int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int mode, const DevOutput& dout,
+                       hipStream_t s) {
+    const int tilesX = (t->width + 15) / 16, tilesY = (t->rows + 15) / 16;
+    const long long blocks = (long long)tilesX * tilesY;
+    PipeArgs a = base_args(ctx, p, t, dout, tilesX, tilesY, blocks);
+    // the cursor and done count: this frame's counter set (zero; the kernel's last workgroup
+    // zeroes them again, so the set stays the pipeline's next one)
+    int rc;
+    bool fresh;
+    if ((rc = begin_counter_sets(ctx, s, fresh))) return rc;
+    if (fresh) ctx->pp_sig = 0;  // (the class lists' counts re-zeroed below)
+    a.sync = (int*)ctx->defer_count.p + 16 * ctx->sync_set;
     const unsigned long long sig = frame_sig(ctx, p, t);
     // samples in parallel (ORT_OPT_PIXEL_SPECULATE, ort_pixel_paths<..., SPEC>): from the second
     // frame of a shape on, when the per-sample state buffers fit kSpecBudget; the first frame
@@ -2539,14 +2592,13 @@ int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int
     const int ns = p->num_samples;
     const size_t slots = (size_t)a.total;
     const int nch = spec_nch(ns);
-    const bool timed_now = !((ctx->debug_flags & 1) || !ctx->launch_times);
+    const bool timed = !((ctx->debug_flags & 1) || !ctx->launch_times);  // per-launch events
     const bool spec_on = ctx->pixel_spec != 0 && nch > 1 && spec_bytes(slots, ns) <= kSpecBudget;
     if (!spec_on) ctx->sp_sig = 0;
     bool spec_frame = false;
     float2 *sp_prev = nullptr, *sp_cur = nullptr;
     if (spec_on) {
         const void* had = ctx->spst.p;
-        int rc;
         if ((rc = ensure(ctx, ctx->spst, 2 * sizeof(float2) * (size_t)nch * slots)) ||
             (rc = ensure(ctx, ctx->spcol, 3 * sizeof(float) * (size_t)ns * slots)) ||
             (rc = ensure(ctx, ctx->spfix, (2 * sizeof(int) + sizeof(float2) + 3 * sizeof(float)) * slots)) ||
@@ -2558,7 +2610,7 @@ int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int
             HIPCHK(ctx, hipMemsetAsync(ctx->spfixn.p, 0, 64, s));
             ctx->sp_tune = 0;
             // untimed contexts cannot compare: speculate on frames of at most kSpecAutoPixels
-            ctx->sp_use = ctx->pixel_spec > 0 || timed_now || pixels <= kSpecAutoPixels;
+            ctx->sp_use = ctx->pixel_spec > 0 || timed || pixels <= kSpecAutoPixels;
         }
         if (ctx->sp_tune >= 3 && ctx->sp_tune < 5 && ctx->frames - ctx->sp_tframe >= ort_ctx::kRing - 2)
             ctx->sp_tune = 2;  // the measured frames' timing slots are being reused: measure again
@@ -2576,7 +2628,7 @@ int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int
             }
         }
         spec_frame = ctx->sp_sig == sig && ctx->sp_use &&
-                     !(ctx->pixel_spec < 0 && timed_now && ctx->sp_tune == 2);  // auto: the measured whole-chain frame
+                     !(ctx->pixel_spec < 0 && timed && ctx->sp_tune == 2);  // auto: the measured whole-chain frame
         a.sp_ctl = (int*)ctx->spfixn.p;
         float2* st0 = (float2*)ctx->spst.p;
         sp_prev = ctx->sp_par ? st0 + (size_t)nch * slots : st0;
@@ -2593,7 +2645,6 @@ int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int
     if (ORT_PIXEL_LPT && !heavy_first && !spec_frame) ctx->pp_sig = 0;
     if (ORT_PIXEL_LPT && heavy_first) {  // last frame's class lists (same shape) and this frame's
         const size_t nb = (size_t)blocks * (kBlock / 64), cnt_b = 2 * kPixelClasses * sizeof(int);
-        int rc;
         if ((rc = ensure(ctx, ctx->pplist, 2 * kPixelClasses * 4 * nb)) || (rc = ensure(ctx, ctx->ppcnt, cnt_b)) ||
             (rc = ensure(ctx, ctx->ppcost, 8 * nb)))
             return rc;
@@ -2629,7 +2680,6 @@ int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int
     }
     const int fslot = (int)(ctx->frames % ort_ctx::kRing);
     ctx->tseg[fslot] = 0;
-    const bool timed = !((ctx->debug_flags & 1) || !ctx->launch_times);
     const int nseg = spec_frame ? 3 : 1;  // SPEC: the samples, the resolve, the fixup list
     for (int j = 0; timed && j < nseg; ++j)
         if (!ctx->tr0[fslot][j]) {
@@ -2641,8 +2691,7 @@ int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int
     if (!spec_frame) {  // every pixel's whole chain (recording its samples' end states when spec_on)
         a.sp_cur = sp_cur;
         const bool rec = spec_on && ctx->sp_use;  // (auto found speculation slower on this shape: no recording)
-        const hipError_t e = rec ? launch_pixel_paths<2>(ctx, mode, deep, lds_scene, lds, blocks, a, s)
-                                 : launch_pixel_paths<0>(ctx, mode, deep, lds_scene, lds, blocks, a, s);
+        const hipError_t e = launch_pixel_paths(rec ? 2 : 0, ctx->device, mode, deep, lds_scene, lds, blocks, a, s);
         if (e != hipSuccess) return hip_fail(ctx, e, "ort_pixel_paths launch");
         if (timed) HIPCHK(ctx, hipEventRecord(ctx->tr1[fslot][0], s));
         if (rec && timed && ctx->sp_tune == 0) ctx->sp_tune = 1;  // auto: a shape's first frame (not measured)
@@ -2681,7 +2730,7 @@ int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int
         hipLaunchKernelGGL(ort_sample_decide, dim3(1), dim3(64), 0, s, a.sp_ctl, (long long)t->width * t->rows, kSpecMovedMax);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(ctx, e, "ort_sample_decide launch");
-        e = launch_pixel_paths<1>(ctx, mode, deep, lds_scene, lds, blocks * nch, as, s);
+        e = launch_pixel_paths(1, ctx->device, mode, deep, lds_scene, lds, blocks * nch, as, s);
         if (e != hipSuccess) return hip_fail(ctx, e, "ort_pixel_paths (samples) launch");
         if (timed) HIPCHK(ctx, hipEventRecord(ctx->tr1[fslot][0], s));
         if (timed) HIPCHK(ctx, hipEventRecord(ctx->tr0[fslot][1], s));
@@ -2691,7 +2740,7 @@ int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int
         if (timed) HIPCHK(ctx, hipEventRecord(ctx->tr0[fslot][2], s));
         // the fixup list (the workgroups beyond what it needs leave at once); in a fall-back frame
         // every pixel's chain, then the count of the pixels that moved
-        e = launch_pixel_paths<2>(ctx, mode, deep, lds_scene, lds, blocks, a, s);
+        e = launch_pixel_paths(2, ctx->device, mode, deep, lds_scene, lds, blocks, a, s);
         if (e != hipSuccess) return hip_fail(ctx, e, "ort_pixel_paths (fixup) launch");
         if (timed) HIPCHK(ctx, hipEventRecord(ctx->tr1[fslot][2], s));
         hipLaunchKernelGGL(ort_sample_moved, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, a, a.sp_ctl + 1);
@@ -2859,42 +2908,22 @@ int render_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, const ort_
             }
         }
     }
-    PipeArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.pp = pixel_params(p);
-    a.S = device_scene(ctx);
-    a.tm = {t->x0, t->width, t->y0, t->rows, t->band_height, t->band_stride};
-    a.tilesX = gridX;
+    PipeArgs a = base_args(ctx, p, t, dout, gridX, tilesY, blocks);
     a.pair = pairs ? 1 : 0;
-    a.tilesY = tilesY;
     a.swizzle = ctx->xcd_swizzle >= 0 ? ctx->xcd_swizzle : ((!pairs && (long long)pix <= kRasterAutoPixels) ? 0 : 2);
     a.xrun_log2 = xcd_run_log2(gridX);
-    a.total = (int)slots;
-    a.exact_only = ctx->exact_only || !ctx->ordered;
     a.refill = ctx->refill;
     a.hit = (int2*)ctx->hit.p;
     a.defer_list = (int*)ctx->defer_list.p;
-    // two sets of 16 counters (deferred count, persistent cursor, heavy list): a launch uses one
-    // and its exact kernel zeroes the other for the next launch; a memset re-zeroes both after a
-    // failed render or a new buffer (sync_ok)
-    if (!ctx->sync_ok) {
-        HIPCHK(ctx, hipMemsetAsync(ctx->defer_count.p, 0, 128, s));
-        ctx->sync_set = 0;
-        ctx->pre_ok = false;  // a failed render may not have listed the next frame's heavy rays
-    }
-    ctx->sync_ok = false;  // until this render has enqueued all its launches
+    bool fresh;
+    if ((rc = begin_counter_sets(ctx, s, fresh))) return rc;
     a.sync = (int*)ctx->defer_count.p;
     a.po = (float4*)ctx->po.p;
     a.pd = (float4*)ctx->pd.p;
     a.pc = (float4*)ctx->pc.p;
     a.prng = (float2*)ctx->prng.p;
     a.pcol = (float4*)ctx->pcol.p;
-    set_output(a, dout);
     a.counters = dcounters;
-#if ORT_ANALYSIS
-    a.wclock = (ulonglong4*)ctx->wclock;
-    a.wclock_n = (int)ctx->wclock_n;
-#endif
     a.mp = ort::mortonPlan(ctx->root_lo, ctx->root_hi);
     // with bounce 0 shaded in the trace kernels every pixel's path ends in a kernel that knows
     // its pixel, so the last sample writes the final pixels itself (no finalize pass)
@@ -2981,9 +3010,6 @@ int render_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, const ort_
     const size_t lds = lds_bytes(mode, ctx->depth, false);
     const size_t lds_exact = lds_bytes(mode, ctx->depth, true);
     const int pblocks = (mode == 0 && ctx->persistent) ? persistent_blocks(ctx->device, dcounters != nullptr, ctx->depth > 8, ctx->depth, lds, blocks) : 0;
-    // the exact kernel: a grid-stride loop over the (usually no) deferred rays; a small grid
-    // dispatches fast
-    const int exact_blocks = 256;
     hipError_t e;
     const int fslot = (int)(ctx->frames % ort_ctx::kRing);  // this frame's timing slot
     ctx->tseg[fslot] = 0;
@@ -3077,22 +3103,13 @@ int render_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, const ort_
                     }
                     at.hsync = hc + 8 * ctx->hpar;
                     at.hsync_next = hc + 8 * (ctx->hpar ^ 1);
-#ifndef ORT_SPLIT_BLOCKS
-#define ORT_SPLIT_BLOCKS 32
-#endif
-                    const int hblocks = ORT_SPLIT_BLOCKS;  // 1024 heavy rays in flight; more loop
-                    const dim3 hg(hblocks), ht(kBlock);
-                    if (ctx->depth > 8 && fmode == 1) hipLaunchKernelGGL((ort_trace_split<true, 1>), hg, ht, lds, ctx->aux_stream, at);
-                    else if (ctx->depth > 8) hipLaunchKernelGGL((ort_trace_split<true, 2>), hg, ht, lds, ctx->aux_stream, at);
-                    else if (fmode == 1) hipLaunchKernelGGL((ort_trace_split<false, 1>), hg, ht, lds, ctx->aux_stream, at);
-                    else hipLaunchKernelGGL((ort_trace_split<false, 2>), hg, ht, lds, ctx->aux_stream, at);
-                    HIPCHK(ctx, hipGetLastError());
+                    if ((e = launch_trace_split(ctx->depth > 8, fmode, at, lds, ctx->aux_stream)) != hipSuccess)
+                        return hip_fail(ctx, e, "hipGetLastError()");
                     HIPCHK(ctx, hipEventRecord(ctx->ev_split, ctx->aux_stream));
                     at.hbits = (const uint32_t*)ctx->hbits.p;
                 }
                 const int tblocks = (prim && pairs) ? (int)(blocks / 2) : (int)blocks;  // a workgroup per tile pair
-                e = dcounters ? launch_trace<true>(mode, prim, at, tblocks, pb, lds, s, fmode)
-                              : launch_trace<false>(mode, prim, at, tblocks, pb, lds, s, fmode);
+                e = launch_trace(dcounters != nullptr, mode, prim, at, tblocks, pb, lds, s, fmode);
                 if (e != hipSuccess) return hip_fail(ctx, e, "trace kernel launch");
                 if (do_split) {
                     HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_split, 0));  // joined before the exact kernel
@@ -3116,16 +3133,8 @@ int render_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, const ort_
                     ctx->tseg[slot] = seg + 1;
                 }
                 if (mode == 0) {
-                    const bool prim = b == 0;
-                    const dim3 g(exact_blocks), t(kBlock);
-                    if (dcounters && fuse) hipLaunchKernelGGL((ort_trace_exact<true, true, 1>), g, t, lds_exact, s, at);
-                    else if (dcounters && prim) hipLaunchKernelGGL((ort_trace_exact<true, true, 0>), g, t, lds_exact, s, at);
-                    else if (dcounters) hipLaunchKernelGGL((ort_trace_exact<true, false, 0>), g, t, lds_exact, s, at);
-                    else if (fuse) hipLaunchKernelGGL((ort_trace_exact<false, true, 1>), g, t, lds_exact, s, at);
-                    else if (fmode == 2) hipLaunchKernelGGL((ort_trace_exact<false, true, 2>), g, t, lds_exact, s, at);
-                    else if (prim) hipLaunchKernelGGL((ort_trace_exact<false, true, 0>), g, t, lds_exact, s, at);
-                    else hipLaunchKernelGGL((ort_trace_exact<false, false, 0>), g, t, lds_exact, s, at);
-                    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, "ort_trace_exact launch");
+                    e = launch_trace_exact(dcounters != nullptr, prim, fmode, at, lds_exact, s);
+                    if (e != hipSuccess) return hip_fail(ctx, e, "ort_trace_exact launch");
                     ctx->sync_set ^= 1;  // it zeroes the other set for the next launch
                     // it listed the next frame's heavy rays: only now may that frame skip its scan
                     if (do_split) ctx->pre_ok = true;
@@ -3213,6 +3222,37 @@ int render_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, const ort_
     return finish_output(ctx, o, dout, t, pitch, stream, s);
 }
 
+// One row per ranged option: the field it writes, its inclusive range, and what a value outside it
+// is answered with.  The options that are not a plain range are ort_set_option's own cases.
+struct OptionRow {
+    int id;
+    int ort_ctx::*field;
+    int lo, hi;
+    const char* bad;
+};
+const OptionRow kOptions[] = {
+    {ORT_OPT_FORCE_LAYOUT, &ort_ctx::force_layout, -1, ORT_LAYOUT_EXPLICIT, "bad layout"},
+    {ORT_OPT_KID_SKIP, &ort_ctx::kid_skip, 0, 2, "ORT_OPT_KID_SKIP: 0, 1 or 2"},
+    {ORT_OPT_XCD_SWIZZLE, &ort_ctx::xcd_swizzle, -1, 2, "xcd swizzle must be -1 (auto), 0, 1 or 2"},
+    {ORT_OPT_SORT_PATHS, &ort_ctx::sort_paths, 0, 2, "sort_paths must be 0, 1 or 2"},
+    {ORT_OPT_HEAVY_FIRST, &ort_ctx::heavy_first, 0, 65535, "ORT_OPT_HEAVY_FIRST: 0 (off) .. 65535 steps"},
+    {ORT_OPT_TILE_PAIRS, &ort_ctx::tile_pairs, -1, 1, "ORT_OPT_TILE_PAIRS: -1 (auto), 0 or 1"},
+    {ORT_OPT_SPLIT_HEAVY, &ort_ctx::split_steps, -1, 65535, "ORT_OPT_SPLIT_HEAVY: -1 (auto), 0 (off) .. 65535 steps"},
+    {ORT_OPT_SPLIT_LEVEL, &ort_ctx::split_level, 0, ORT_COMPACT_MAX_DEPTH, "ORT_OPT_SPLIT_LEVEL: 0 (auto) .. 10"},
+    {ORT_OPT_PIXEL_PATHS, &ort_ctx::pixel_paths, -1, 1, "ORT_OPT_PIXEL_PATHS: -1 (auto), 0 or 1"},
+    {ORT_OPT_PIXEL_SPECULATE, &ort_ctx::pixel_spec, -1, 1, "ORT_OPT_PIXEL_SPECULATE: -1 (auto), 0 or 1"},
+    {ORT_OPT_PIXEL_HEAVY_FIRST, &ort_ctx::pixel_heavy_first, -1, 1, "ORT_OPT_PIXEL_HEAVY_FIRST: -1 (auto), 0 or 1"},
+    {ORT_OPT_PIXEL_LDS_SCENE, &ort_ctx::pixel_lds_scene, 0, 1, "ORT_OPT_PIXEL_LDS_SCENE: 0 or 1"},
+    {ORT_OPT_LAUNCH_TIMES, &ort_ctx::launch_times, 0, 1, "ORT_OPT_LAUNCH_TIMES: 0 or 1"},
+#if ORT_ANALYSIS  // analysis: 1 no trace-timing events, 2 no queued heavy scan
+    {ORT_OPT_DEBUG_FLAGS, &ort_ctx::debug_flags, 0, 3, "ORT_OPT_DEBUG_FLAGS: 0 .. 3"},
+#endif
+    {ORT_OPT_HEAVY_PRIO, &ort_ctx::heavy_prio, 0, 65535, "ORT_OPT_HEAVY_PRIO: 0 (off) .. 65535 steps"},
+    {ORT_OPT_COST_ORDER, &ort_ctx::cost_order, 0, 1, "ORT_OPT_COST_ORDER: 0 or 1"},
+    {ORT_OPT_SORT_BOUND, &ort_ctx::sort_bound, 0, INT_MAX, "ORT_OPT_SORT_BOUND must be >= 0"},  // no upper bound
+    {ORT_OPT_REFILL, &ort_ctx::refill, 1, 64, "refill must be 1..64"},
+};
+
 }  // namespace
 
 extern "C" {
@@ -3223,9 +3263,12 @@ int ort_create(int device, ort_ctx** out) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess) return hip_fail(nullptr, e, "hipGetDeviceCount");
-    if (device < 0 || device >= n)
-        return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_create: device " + std::to_string(device) + " not present (" +
-                                                      std::to_string(n) + " visible)");
+    if (device < 0 || device >= n) {
+        std::string have;
+        [[clang::noinline]] have = std::to_string(n);  // (called, not inlined: the library keeps exporting its copy)
+        return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_create: device " + std::to_string(device) + " not present (" + have +
+                                                      " visible)");
+    }
     ort_ctx* c = new (std::nothrow) ort_ctx();
     if (!c) return fail(nullptr, ORT_ERR_OUT_OF_MEMORY, "ort_create: out of host memory");
     c->device = device;
@@ -3307,11 +3350,6 @@ const char* ort_last_error(const ort_ctx* ctx) { return ctx ? ctx->err.c_str() :
 
 int ort_set_option(ort_ctx* ctx, int option, int value) {
     if (!ctx) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_set_option: null ctx");
-    if (option == ORT_OPT_FORCE_LAYOUT) {
-        if (value < -1 || value > ORT_LAYOUT_EXPLICIT) return fail(ctx, ORT_ERR_INVALID_ARG, "bad layout");
-        ctx->force_layout = value;
-        return ORT_OK;
-    }
     if (option == ORT_OPT_PERSISTENT) {
         if (value == 1)  // removed in round 4
             return fail(ctx, ORT_ERR_UNSUPPORTED, "ORT_OPT_PERSISTENT 1 (every trace persistent) was removed (C5 -19 %)");
@@ -3319,73 +3357,17 @@ int ort_set_option(ort_ctx* ctx, int option, int value) {
         ctx->persistent = value;
         return ORT_OK;
     }
-    if (option == ORT_OPT_KID_SKIP) {
-        if (value < 0 || value > 2) return fail(ctx, ORT_ERR_INVALID_ARG, "ORT_OPT_KID_SKIP: 0, 1 or 2");
-        ctx->kid_skip = value;
+    if (option == ORT_OPT_EXACT_TRAVERSAL) {
+        ctx->exact_only = value ? 1 : 0;
         return ORT_OK;
     }
-    if (option == ORT_OPT_XCD_SWIZZLE) {
-        if (value < -1 || value > 2) return fail(ctx, ORT_ERR_INVALID_ARG, "xcd swizzle must be -1 (auto), 0, 1 or 2");
-        ctx->xcd_swizzle = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_SORT_PATHS) {
-        if (value < 0 || value > 2) return fail(ctx, ORT_ERR_INVALID_ARG, "sort_paths must be 0, 1 or 2");
-        ctx->sort_paths = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_HEAVY_FIRST) {
-        if (value < 0 || value > 65535) return fail(ctx, ORT_ERR_INVALID_ARG, "ORT_OPT_HEAVY_FIRST: 0 (off) .. 65535 steps");
-        ctx->heavy_first = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_TILE_PAIRS) {
-        if (value < -1 || value > 1) return fail(ctx, ORT_ERR_INVALID_ARG, "ORT_OPT_TILE_PAIRS: -1 (auto), 0 or 1");
-        ctx->tile_pairs = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_SPLIT_HEAVY) {
-        if (value < -1 || value > 65535) return fail(ctx, ORT_ERR_INVALID_ARG, "ORT_OPT_SPLIT_HEAVY: -1 (auto), 0 (off) .. 65535 steps");
-        ctx->split_steps = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_SPLIT_LEVEL) {
-        if (value < 0 || value > ORT_COMPACT_MAX_DEPTH) return fail(ctx, ORT_ERR_INVALID_ARG, "ORT_OPT_SPLIT_LEVEL: 0 (auto) .. 10");
-        ctx->split_level = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_PIXEL_PATHS) {
-        if (value < -1 || value > 1) return fail(ctx, ORT_ERR_INVALID_ARG, "ORT_OPT_PIXEL_PATHS: -1 (auto), 0 or 1");
-        ctx->pixel_paths = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_PIXEL_SPECULATE) {
-        if (value < -1 || value > 1) return fail(ctx, ORT_ERR_INVALID_ARG, "ORT_OPT_PIXEL_SPECULATE: -1 (auto), 0 or 1");
-        ctx->pixel_spec = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_PIXEL_HEAVY_FIRST) {
-        if (value < -1 || value > 1) return fail(ctx, ORT_ERR_INVALID_ARG, "ORT_OPT_PIXEL_HEAVY_FIRST: -1 (auto), 0 or 1");
-        ctx->pixel_heavy_first = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_PIXEL_LDS_SCENE) {
-        if (value < 0 || value > 1) return fail(ctx, ORT_ERR_INVALID_ARG, "ORT_OPT_PIXEL_LDS_SCENE: 0 or 1");
-        ctx->pixel_lds_scene = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_LAUNCH_TIMES) {
-        if (value < 0 || value > 1) return fail(ctx, ORT_ERR_INVALID_ARG, "ORT_OPT_LAUNCH_TIMES: 0 or 1");
-        ctx->launch_times = value;
-        return ORT_OK;
-    }
-#if ORT_ANALYSIS
-    if (option == ORT_OPT_DEBUG_FLAGS) {  // analysis: 1 no trace-timing events, 2 no queued heavy scan
-        if (value < 0 || value > 3) return fail(ctx, ORT_ERR_INVALID_ARG, "ORT_OPT_DEBUG_FLAGS: 0 .. 3");
-        ctx->debug_flags = value;
-        return ORT_OK;
-    }
-#else
+    for (const OptionRow& r : kOptions)
+        if (r.id == option) {
+            if (value < r.lo || value > r.hi) return fail(ctx, ORT_ERR_INVALID_ARG, r.bad);
+            ctx->*r.field = value;
+            return ORT_OK;
+        }
+#if !ORT_ANALYSIS
     if (option == ORT_OPT_DEBUG_FLAGS)
         return fail(ctx, ORT_ERR_UNSUPPORTED, "ORT_OPT_DEBUG_FLAGS: analysis library only (libort_analysis.so)");
 #endif
@@ -3394,30 +3376,6 @@ int ort_set_option(ort_ctx* ctx, int option, int value) {
                                                   (option == 5 ? "packet walk" : option == 7 ? "wave queue"
                                                                                              : "longest-first workgroups") +
                                                   ": measured slower, DESIGN.md 4)");
-    if (option == ORT_OPT_HEAVY_PRIO) {
-        if (value < 0 || value > 65535) return fail(ctx, ORT_ERR_INVALID_ARG, "ORT_OPT_HEAVY_PRIO: 0 (off) .. 65535 steps");
-        ctx->heavy_prio = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_COST_ORDER) {
-        if (value < 0 || value > 1) return fail(ctx, ORT_ERR_INVALID_ARG, "ORT_OPT_COST_ORDER: 0 or 1");
-        ctx->cost_order = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_SORT_BOUND) {
-        if (value < 0) return fail(ctx, ORT_ERR_INVALID_ARG, "ORT_OPT_SORT_BOUND must be >= 0");
-        ctx->sort_bound = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_REFILL) {
-        if (value < 1 || value > 64) return fail(ctx, ORT_ERR_INVALID_ARG, "refill must be 1..64");
-        ctx->refill = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_EXACT_TRAVERSAL) {
-        ctx->exact_only = value ? 1 : 0;
-        return ORT_OK;
-    }
     return fail(ctx, ORT_ERR_INVALID_ARG, "unknown option");
 }
 
@@ -3469,10 +3427,8 @@ int ort_scene_get_info(const ort_ctx* ctx, ort_scene_info* info) {
     info->n_indices = ctx->n_indices;
     info->layout = ctx->layout;
     info->tree_depth = ctx->depth;
-    const DevBuf* all[] = {&ctx->sph_cr, &ctx->sph_ma, &ctx->sph_fr, &ctx->node, &ctx->kid, &ctx->nk, &ctx->leaf_sph, &ctx->leaf_idx,
-                           &ctx->planes, &ctx->lds_img, &ctx->lds_rev, &ctx->nodeA, &ctx->nodeB, &ctx->cnt, &ctx->indices};
     int64_t b = 0;
-    for (const DevBuf* d : all) b += (int64_t)d->bytes;
+    each_scene_buffer(*ctx, [&](const DevBuf& d) { b += (int64_t)d.bytes; });
     info->device_bytes = b;
     return ORT_OK;
 }
