@@ -12,7 +12,7 @@ HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -ffp-contract=off -fno-fast-ma
 HOST_SRCS := octree.cpp scene.cpp host_abi.cpp layout.cpp raytracer.cpp
 HOST_OBJS := $(addprefix $(OBJ)/,$(HOST_SRCS:.cpp=.o))
 HIP_OBJS := $(OBJ)/ort_kernel.o $(OBJ)/gpu_build.o $(OBJ)/group.o
-HDRS := $(wildcard $(SRC)/*.h) $(SRC)/prebuilt_scene.inc include/ort.h include/ort_math.h
+HDRS := $(wildcard $(SRC)/*.h) $(SRC)/prebuilt_scene.inc $(SRC)/ray_query.inc include/ort.h include/ort_math.h
 
 # The analysis library (test/analysis surface: ort_debug_* host emulation and walk statistics,
 # ORT_OPT_DEBUG_FLAGS) -- the same sources with -DORT_ANALYSIS=1; the CPU suite and tools/
@@ -55,7 +55,10 @@ $(LIB): $(HOST_OBJS) $(HIP_OBJS)
 	@mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -ldl -Wl,-soname,libort.so
 
-examples: build/ort_main build/stats_row
+examples: build/ort_main build/stats_row build/trace_rays
+
+build/trace_rays: tests/cpp/trace_rays.cpp $(LIB) $(HDRS)
+	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ tests/cpp/trace_rays.cpp -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
 
 build/stats_row: tests/cpp/stats_row.cpp $(LIB) $(HDRS)
 	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ tests/cpp/stats_row.cpp -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
@@ -79,8 +82,9 @@ SAN_HOST := $(addprefix $(SANOBJ)/,$(HOST_SRCS:.cpp=.o))
 SAN_HIP := $(SANOBJ)/ort_kernel.o $(SANOBJ)/gpu_build.o $(SANOBJ)/group.o
 HIP_SAN := $(foreach f,address undefined,-Xarch_host -fsanitize=$(f)) -Xarch_host -fno-sanitize-recover=undefined
 
-san: build/san/san_check
+san: build/san/san_check build/san/san_query
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/san_check
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/san_query
 
 $(SANOBJ)/%.o: $(SRC)/%.cpp $(HDRS)
 	@mkdir -p $(SANOBJ)
@@ -97,6 +101,14 @@ $(SANOBJ)/ort_oracle.o: oracle/ort_oracle.c oracle/ort_oracle.h include/ort_math
 $(SANOBJ)/san_check.o: tests/cpp/san_check.cpp $(HDRS) oracle/ort_oracle.h
 	@mkdir -p $(SANOBJ)
 	$(CLANGXX) $(SAN) -std=c++17 -I$(SRC) -Ioracle -c $< -o $@
+
+# the ray queries' host code (ort_debug_query_rays: render_core.h query_ray) under the same sanitizers
+$(SANOBJ)/san_query.o: tests/cpp/san_query.cpp $(HDRS)
+	@mkdir -p $(SANOBJ)
+	$(CLANGXX) $(SAN) -std=c++17 -I$(SRC) -c $< -o $@
+
+build/san/san_query: $(SANOBJ)/san_query.o $(SAN_HOST) $(SAN_HIP)
+	$(HIPCC) --offload-arch=$(ARCH) $(SAN) -o $@ $^ -ldl
 
 build/san/san_check: $(SANOBJ)/san_check.o $(SAN_HOST) $(SAN_HIP) $(SANOBJ)/ort_oracle.o
 	$(HIPCC) --offload-arch=$(ARCH) $(SAN) -o $@ $^ -ldl

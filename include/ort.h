@@ -325,6 +325,54 @@ int ort_frame_trace_times_ms(ort_ctx* ctx, int n, float* ms, int32_t* launches);
  * pixels, the reference-layout work counters ORT_COUNT_* (counts[ORT_COUNT_N]). */
 int ort_count_traffic(ort_ctx* ctx, const ort_params* params, const ort_tile* tile, uint64_t* counts);
 
+/* ---- ray queries: what does this ray hit, and where? (picking, visibility, probe placement) ----
+ * ort_trace_rays walks caller-supplied rays through the uploaded scene and returns, per ray, what
+ * the shader's intersectScene(ray, 0.001, MAXFLOAT) finds (glsl:500-506), bit for bit: the walk
+ * the pixels are made with.  That walk leaves the tree after the first leaf that holds a hit
+ * (SURVEY.md F6), so with use_octree = 1 the sphere reported is the one that is DRAWN along the
+ * ray, which is not always the geometrically nearest one; use_octree = 0 (bruteForceIntersect)
+ * tests every sphere and reports the nearest, the lowest index among equals.
+ *   ray     origin and direction, used as given: nothing is normalised, and t is in units of the
+ *           direction's length (Sphere_hit).  Degenerate rays (zero, infinite or NaN components)
+ *           terminate and miss.
+ *   hit     t and the index of the sphere in the uploaded sphere arrays; a miss is {0.0f, -1}.
+ *   normals NULL, or 3 floats per ray: IntersectInfo.normal = ((o + t d) - c) / r in float32,
+ *           three zeros for a miss.
+ * on_device != 0: rays, hits and normals are device pointers on the context's device; else host
+ * pointers, staged through grow-only device buffers the context owns.  stream: as ort_render
+ * (NULL: the context's stream and a synchronous call; a handle: stream-ordered, no host wait
+ * inside the call -- host pointers always wait for their copies).  ORT_QUERY_SORT walks the rays
+ * in the coherence order of the bounce paths (one radix sort of (key, index)); the records stay
+ * in input order and hold the same values.  It applies to the octree walk of the compact layout
+ * and is accepted and ignored elsewhere.  ORT_OPT_KID_SKIP, ORT_OPT_EXACT_TRAVERSAL and
+ * ORT_OPT_REFILL apply as they do to bounce walks (same records under every value).  A query
+ * keeps its own buffers and counters: it reads and writes no per-frame render state, so frames
+ * before and after it are the frames without it.  (Queries of one context share those buffers among
+ * themselves: order them on one stream, or let one finish before the next starts on another.)
+ * n_rays == 0: ORT_OK, nothing launched.  ORT_ERR_INVALID_ARG, before anything is launched: NULL
+ * q, n_rays < 0 or > 2^30, NULL rays or hits with n_rays > 0, unknown flag bits, reserved != 0,
+ * pointers that are not 4-byte aligned.  ORT_ERR_NO_SCENE: no scene, or use_octree = 1 on a
+ * scene uploaded without a tree.  Not in scope: a caller-chosen (t_min, t_max), camera-ray
+ * generation, queries on an ort_group. */
+typedef struct ort_ray     { float origin[3]; float direction[3]; } ort_ray;   /* 24 bytes */
+typedef struct ort_ray_hit { float t; int32_t sphere; } ort_ray_hit;           /* 8 bytes */
+#define ORT_QUERY_SORT 1
+typedef struct ort_ray_query {
+    const ort_ray* rays;
+    int64_t n_rays;
+    ort_ray_hit* hits;     /* n_rays records */
+    float* normals;        /* NULL, or 3 floats per ray */
+    int32_t on_device;     /* != 0: all three pointers are device pointers on ctx's device */
+    int32_t use_octree;    /* 1: the octree walk; 0: bruteForceIntersect (as ort_params.use_octree) */
+    int32_t flags;         /* 0 or ORT_QUERY_SORT */
+    int32_t reserved;      /* 0 */
+} ort_ray_query;
+int ort_trace_rays(ort_ctx* ctx, const ort_ray_query* q, void* stream);
+
+/* Duration in milliseconds of the last ort_trace_rays' kernels (the sort's included, the host
+ * copies not), from HIP events on its stream.  Only valid once that stream has passed the query. */
+int ort_last_query_ms(ort_ctx* ctx, float* ms);
+
 /* ---- several GPUs, one process --------------------------------------
  * The reference renders on one GL context; a caller of Raytracer::render() reaches the 8-GPU
  * configs through a group: one context per listed device (scene replicated), the frame cut

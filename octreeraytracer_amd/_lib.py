@@ -64,6 +64,7 @@ EXPORTED_SYMBOLS = (
     "ort_group_last_frame_ms", "ort_group_create_pipelined", "ort_group_frames_in_flight", "ort_group_submit",
     "ort_group_wait", "ort_group_set_timeout",
     "ort_render_ex", "ort_group_submit_fmt", "ort_group_render_fmt",
+    "ort_trace_rays", "ort_last_query_ms",
 )
 ORT_GROUP_TRANSPORT_RCCL = 0
 ORT_GROUP_TRANSPORT_COPY = 1
@@ -75,6 +76,8 @@ ORT_PLACE_FRAME = 1
 FORMATS = {"rgb32f": ORT_FORMAT_RGB32F, "rgba8": ORT_FORMAT_RGBA8}
 PLACEMENTS = {"tile": ORT_PLACE_TILE, "frame": ORT_PLACE_FRAME}
 FORMAT_BPP = {ORT_FORMAT_RGB32F: 12, ORT_FORMAT_RGBA8: 4}
+# ort_ray_query.flags (ort_trace_rays)
+ORT_QUERY_SORT = 1
 
 
 class OrtParams(C.Structure):
@@ -96,6 +99,21 @@ class OrtOutput(C.Structure):
     _fields_ = [
         ("data", C.c_void_p), ("is_device", C.c_int32), ("format", C.c_int32), ("placement", C.c_int32),
         ("reserved", C.c_int32), ("row_pitch_bytes", C.c_int64),
+    ]
+
+
+class OrtRay(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("direction", C.c_float * 3)]
+
+
+class OrtRayHit(C.Structure):
+    _fields_ = [("t", C.c_float), ("sphere", C.c_int32)]
+
+
+class OrtRayQuery(C.Structure):
+    _fields_ = [
+        ("rays", C.c_void_p), ("n_rays", C.c_int64), ("hits", C.c_void_p), ("normals", C.c_void_p),
+        ("on_device", C.c_int32), ("use_octree", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
     ]
 
 
@@ -139,6 +157,8 @@ def _declare(lib, debug: str = "none"):
         "ort_get_stream": (C.c_int, [_vp, C.POINTER(C.c_void_p)]),
         "ort_render": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), _vp, C.c_int, _vp]),
         "ort_render_ex": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(OrtOutput), _vp]),
+        "ort_trace_rays": (C.c_int, [_vp, C.POINTER(OrtRayQuery), _vp]),
+        "ort_last_query_ms": (C.c_int, [_vp, _fp]),
         "ort_last_kernel_ms": (C.c_int, [_vp, _fp]),
         "ort_last_trace_ms": (C.c_int, [_vp, _fp]),
         "ort_trace_times_ms": (C.c_int, [_vp, C.c_int, _fp]),
@@ -179,6 +199,8 @@ def _declare(lib, debug: str = "none"):
         "ort_debug_pack_rgba8": (C.c_int, [_fp, C.c_int64, C.POINTER(C.c_uint32)]),
         "ort_debug_trace_rays": (C.c_int, [_fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip, C.c_int64, _fp,
                                            C.c_int32, C.c_int32, _ip]),
+        "ort_debug_query_rays": (C.c_int, [_fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip, C.c_int64, C.c_int32,
+                                           C.c_int32, _fp, C.c_int64, _vp, _fp]),
         "ort_debug_split_rays": (C.c_int, [_fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip, C.c_int64, _fp,
                                            C.c_int32, C.c_int32, C.c_int32, _ip]),
         "ort_debug_emulate_render": (C.c_int, [_fp, _fp, _fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip,

@@ -54,6 +54,15 @@ int ort_debug_trace_rays(const float* sphere_center_radius, int32_t n_spheres, c
                          const float* node_max, const int32_t* children_offset, const int32_t* objects_offset,
                          const int32_t* object_count, int32_t n_nodes, const int32_t* object_indices, int64_t n_indices,
                          const float* rays, int32_t n_rays, int32_t bounce, int32_t* out);
+// TEST-ONLY: ort_trace_rays on the host CPU: render_core.h query_ray (the kernels' own per-ray
+// function) for every ray (origin.xyz, direction.xyz in rays[6 i]) -- layout ORT_LAYOUT_COMPACT
+// or ORT_LAYOUT_EXPLICIT with use_octree 1, brute force with use_octree 0.  hits: n_rays
+// records; normals: NULL or 3 floats per ray.
+int ort_debug_query_rays(const float* sphere_center_radius, int32_t n_spheres, const float* node_min,
+                         const float* node_max, const int32_t* children_offset, const int32_t* objects_offset,
+                         const int32_t* object_count, int32_t n_nodes, const int32_t* object_indices, int64_t n_indices,
+                         int32_t layout, int32_t use_octree, const float* rays, int64_t n_rays, ort_ray_hit* hits,
+                         float* normals);
 // ANALYSIS-ONLY: lane overlap of sampled 8x8 primary-ray blocks (tools/wave_stats.py).
 int ort_debug_wave_stats(const float* sphere_center_radius, const float* sphere_mat_albedo,
                          const float* sphere_fuzz_ri, int32_t n_spheres, const float* node_min,

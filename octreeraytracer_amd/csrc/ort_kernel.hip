@@ -2008,6 +2008,14 @@ struct ort_ctx {
     DevBuf skeys, skeys2, svals;  // coherence sort
     DevBuf key_spread;            // its origin-code tables for the scene's root box (path_key.h)
     float spread_box[6] = {0, 0, 0, 0, 0, 0};  // the root box key_spread was built for
+    // ray queries (ort_trace_rays, ray_query.inc): their own buffers and counters, none of the
+    // per-frame state above -- the staging of host pointers (grow-only), the defer list and the
+    // {deferred count, cursor} counters, ORT_QUERY_SORT's keys and lists, the timing events
+    DevBuf q_rays, q_hits, q_normals;
+    DevBuf q_defer, q_sync;
+    DevBuf q_keys, q_keys2, q_vals, q_list, q_temp;
+    hipEvent_t qev0 = nullptr, qev1 = nullptr;
+    bool q_timed = false;
 };
 
 namespace {
@@ -3324,6 +3332,11 @@ int ort_destroy(ort_ctx* ctx) {
                       &ctx->qlist, &ctx->qlist2, &ctx->qcount, &ctx->qtemp, &ctx->skeys, &ctx->skeys2, &ctx->svals, &ctx->key_spread,
                       &ctx->pcost, &ctx->bcost, &ctx->hbits, &ctx->hlist, &ctx->hcnt, &ctx->pplist, &ctx->ppcnt, &ctx->ppcost, &ctx->spst, &ctx->spcol, &ctx->spfix, &ctx->spfixn};
     for (DevBuf* b : pipe) free_buf(*b);
+    DevBuf* query[] = {&ctx->q_rays, &ctx->q_hits, &ctx->q_normals, &ctx->q_defer, &ctx->q_sync,
+                       &ctx->q_keys, &ctx->q_keys2, &ctx->q_vals, &ctx->q_list, &ctx->q_temp};
+    for (DevBuf* b : query) free_buf(*b);
+    if (ctx->qev0) (void)hipEventDestroy(ctx->qev0);
+    if (ctx->qev1) (void)hipEventDestroy(ctx->qev1);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (int i = 0; i < ort_ctx::kRing; ++i)
@@ -4143,3 +4156,7 @@ int64_t ort_debug_walk_steps(const float* cr, const float* ma, const float* fr, 
 #endif  // ORT_ANALYSIS
 
 }  // extern "C"
+
+// Ray queries (ort_trace_rays, ort_last_query_ms, ort_debug_query_rays): after the render path, so
+// that its kernels keep their places in the code object.
+#include "ray_query.inc"

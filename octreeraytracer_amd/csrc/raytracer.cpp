@@ -146,6 +146,18 @@ int Raytracer::render(const Camera& cam, const ort_tile& tile, const ort_output&
     return ort_render_ex(ctx, &p, &tile, &output, stream);
 }
 
+int Raytracer::traceRays(const ort_ray* rays, int64_t n, ort_ray_hit* hits, float* normals) {
+    if (!ctx && !group && !initialize()) return ORT_ERR_HIP;
+    if (group) return ORT_ERR_UNSUPPORTED;  // queries run on one context
+    if (!sceneReady) {
+        setupScene();
+        setupBuffers();
+        if (!sceneReady) return ORT_ERR_INVALID_ARG;
+    }
+    const ort_ray_query q = {rays, n, hits, normals, 0, cfg.useOctree, 0, 0};
+    return ort_trace_rays(ctx, &q, nullptr);
+}
+
 int Raytracer::render(const Camera& cam, float* rgb) {
     if (!ctx && !group && !initialize()) return ORT_ERR_HIP;
     if (group) {

@@ -82,6 +82,12 @@ public:
     // The same with the output described by an ort_output (include/ort.h ort_render_ex): RGBA8
     // as the GL default framebuffer holds it, a row pitch, the tile placed into a whole frame.
     int render(const Camera& cam, const ort_tile& tile, const ort_output& output, void* stream);
+    // Ray queries (include/ort.h ort_trace_rays): what each of n rays hits in the current scene
+    // -- hits[i] = {t, sphere index in getSpheres()} ({0, -1}: a miss), normals (nullptr, or 3
+    // floats per ray) the surface normals -- by the walk the frames are drawn with (cfg.useOctree).
+    // Host pointers; builds and uploads the scene on first use, like render.  Single-device
+    // configurations only (a group: ORT_ERR_UNSUPPORTED).
+    int traceRays(const ort_ray* rays, int64_t n, ort_ray_hit* hits, float* normals = nullptr);
 
     Camera camera;  // the reference keeps a global Camera (src/main.cpp:18); pose set like main()
     const RaytracerConfig& config() const { return cfg; }

@@ -1862,4 +1862,49 @@ ORT_FN V3 shade_pixel(const PixelParams& P, const KScene& S, const float* planes
     return finish_pixel(col, P.ns);
 }
 
+// --- ray queries (ort_trace_rays): a caller's ray -> {t, sphere, normal} ---
+// What intersectScene(ray, 0.001, MAXFLOAT) finds, as the caller sees it: t, the index of the
+// hit sphere in the uploaded arrays and IntersectInfo.normal; a miss is {0, -1, (0, 0, 0)}.
+struct RayHit {
+    float t;
+    int sphere;
+    V3 normal;
+};
+
+// The record of a finished walk (hit, t, entry as the traversals return them).  sphere and the
+// normal are hit_record's: the same index by layout, the same float32 operations in the same
+// order.  want_normal: the three divisions only where the caller asked for normals.
+template <int MODE>
+ORT_FN RayHit query_hit(const KScene& S, const Ray& r, bool hit, float t, int entry, bool want_normal) {
+    RayHit q;
+    q.t = 0.0f;
+    q.sphere = -1;
+    q.normal = mk(0.0f, 0.0f, 0.0f);
+    if (!hit) return q;
+    q.t = t;
+    q.sphere = MODE == 0 ? S.leaf_idx[entry] : (MODE == 1 ? S.indices[entry] : entry);
+    if (want_normal) {
+        const float4 sp = S.sph_cr[q.sphere];
+        const V3 p = mk(r.o.x + t * r.d.x, r.o.y + t * r.d.y, r.o.z + t * r.d.z);
+        q.normal = mk((p.x - sp.x) / sp.w, (p.y - sp.y) / sp.w, (p.z - sp.z) / sp.w);
+    }
+    return q;
+}
+
+// One ray query, whole: the walk a bounce ray of the render path takes (trace_ray, bounce: the
+// fast walk without inline leaf children where rank_lut is given and fast_prepare takes the ray,
+// the literal exact walk otherwise; the explicit layout's stack walk; brute force) and its
+// record.  The host emulation and the per-lane / exact query kernels call this; the persistent
+// query kernel runs the same fast walk a step at a time and ends in query_hit.
+template <int MODE, class Frames>
+ORT_FN RayHit query_ray(const KScene& S, const float* planes, const float* planes_b, const uint8_t* rank_lut,
+                        const Ray& r, Frames& fr, int* snode, float* stmin, bool want_normal) {
+    Counters cnt;
+    for (int k = 0; k < 6; ++k) cnt.v[k] = 0;
+    float t;
+    int entry;
+    const int tr = trace_ray<MODE, false>(S, planes, rank_lut, r, false, t, entry, fr, snode, stmin, cnt, true, planes_b);
+    return query_hit<MODE>(S, r, tr == ORT_TRACE_HIT, t, entry, want_normal);
+}
+
 }  // namespace ort

@@ -328,6 +328,96 @@ class Renderer:
         self._check(self._lib.ort_render_ex(self._ctx, C.byref(p), C.byref(t), C.byref(o), s))
         return out
 
+    # -- ray queries ------------------------------------------------------------------
+    def trace_rays(self, rays, *, use_octree=True, sort=False, normals=False, out=None, stream=None, n=None):
+        """What does each ray hit, and where (ort_trace_rays, include/ort.h): per ray the shader's
+        intersectScene(ray, 0.001, MAXFLOAT) -- t (in units of the direction's length; directions
+        are used as given) and the index of the hit sphere in the uploaded arrays, (0.0, -1) for a
+        miss; with normals the unit-sphere normal ((o + t d) - c) / r, zeros for a miss.  With
+        use_octree the walk is the one the pixels are made with: it leaves the tree after the first
+        leaf holding a hit, so the sphere is the one drawn, not always the nearest.
+
+        rays: a C-contiguous (n, 6) float32 numpy array (origin, direction) -> returns
+        (t float32 (n,), sphere int32 (n,)) and, with normals=True, an (n, 3) float32 array; out
+        may be an (n, 2) int32 array to receive the records {t bits, sphere}.
+        rays: a contiguous (n, 6) float32 torch CUDA tensor on this device, or a device pointer
+        (int) with n -> everything stays on the device: returns out, an (n, 2) int32 tensor of
+        {t bits, sphere} (allocated when None; a pointer needs out given), and with normals the
+        (n, 3) float32 normals tensor (normals=True allocates it; a tensor or pointer is used).
+        sort: walk the rays in coherence order (ORT_QUERY_SORT; same records, same order).
+        stream: as render()."""
+        flags = L.ORT_QUERY_SORT if sort else 0
+        s = C.c_void_p(int(stream)) if stream else None
+        q = L.OrtRayQuery(None, 0, None, None, 0, 1 if use_octree else 0, flags, 0)
+        if isinstance(rays, np.ndarray):
+            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 6 or not rays.flags.c_contiguous:
+                raise ValueError(f"trace_rays: rays must be a C-contiguous (n, 6) float32 array (got {rays.dtype}, "
+                                 f"shape {rays.shape}, contiguous={rays.flags.c_contiguous})")
+            nr = rays.shape[0]
+            if n is not None and int(n) != nr:
+                raise ValueError(f"trace_rays: n = {n} but rays holds {nr}")
+            if out is None:
+                out = np.empty((nr, 2), np.int32)
+            if (not isinstance(out, np.ndarray) or out.dtype != np.int32 or not out.flags.c_contiguous or
+                    out.nbytes < 8 * nr):
+                raise ValueError(f"trace_rays: out must be a C-contiguous int32 numpy array of >= {8 * nr} bytes")
+            if not isinstance(normals, (bool, np.bool_)):
+                raise ValueError("trace_rays: with host rays, normals is True or False")
+            nrm = np.zeros((nr, 3), np.float32) if normals else None
+            q.rays, q.n_rays = rays.ctypes.data_as(C.c_void_p), nr
+            q.hits = out.ctypes.data_as(C.c_void_p)
+            q.normals = nrm.ctypes.data_as(C.c_void_p) if normals else None
+            self._check(self._lib.ort_trace_rays(self._ctx, C.byref(q), s))
+            rec = out.reshape(-1)[:2 * nr].reshape(nr, 2)
+            t, sph = np.ascontiguousarray(rec[:, 0]).view(np.float32), np.ascontiguousarray(rec[:, 1])
+            return (t, sph, nrm) if normals else (t, sph)
+
+        def device_arg(x, what, dtype_name, need):  # a torch CUDA tensor on this device, or a pointer
+            if hasattr(x, "data_ptr"):
+                nbytes = x.numel() * x.element_size()
+                if str(x.dtype) != "torch." + dtype_name or not x.is_contiguous() or nbytes < need:
+                    raise ValueError(f"trace_rays: {what} must be a contiguous {dtype_name} tensor of >= {need} bytes "
+                                     f"(got {x.dtype}, {nbytes} bytes, contiguous={x.is_contiguous()})")
+                if x.device.type != "cuda" or x.device.index != self.device:
+                    raise ValueError(f"trace_rays: {what} is on {x.device}, the context traces on cuda:{self.device}")
+                return x.data_ptr()
+            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+                raise ValueError(f"trace_rays: {what} must be a torch CUDA tensor or a device pointer (int)")
+            return int(x)
+
+        if hasattr(rays, "data_ptr"):
+            if rays.dim() != 2 or rays.shape[1] != 6:
+                raise ValueError(f"trace_rays: rays must have shape (n, 6) (got {tuple(rays.shape)})")
+            nr = rays.shape[0]
+            if n is not None and int(n) != nr:
+                raise ValueError(f"trace_rays: n = {n} but rays holds {nr}")
+        else:
+            if n is None or int(n) < 0:
+                raise ValueError("trace_rays: a device pointer needs n, the number of rays")
+            nr = int(n)
+            if out is None or (isinstance(normals, (bool, np.bool_)) and normals):
+                raise ValueError("trace_rays: a device pointer needs out (and normals, where wanted) given")
+        q.rays, q.n_rays = C.c_void_p(device_arg(rays, "rays", "float32", 24 * nr)), nr
+        if out is None or (isinstance(normals, (bool, np.bool_)) and normals):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if out is None:
+                out = torch.empty((nr, 2), dtype=torch.int32, device=dev)
+            if isinstance(normals, (bool, np.bool_)) and normals:
+                normals = torch.empty((nr, 3), dtype=torch.float32, device=dev)
+        want_normals = not isinstance(normals, (bool, np.bool_))
+        q.hits = C.c_void_p(device_arg(out, "out", "int32", 8 * nr))
+        q.normals = C.c_void_p(device_arg(normals, "normals", "float32", 12 * nr)) if want_normals else None
+        q.on_device = 1
+        self._check(self._lib.ort_trace_rays(self._ctx, C.byref(q), s))
+        return (out, normals) if want_normals else out
+
+    def last_query_ms(self) -> float:
+        """The last trace_rays' kernels (its sort included), from HIP events on its stream."""
+        ms = C.c_float()
+        self._check(self._lib.ort_last_query_ms(self._ctx, C.byref(ms)))
+        return ms.value
+
     def last_kernel_ms(self) -> float:
         ms = C.c_float()
         self._check(self._lib.ort_last_kernel_ms(self._ctx, C.byref(ms)))
@@ -398,3 +488,29 @@ def emulate_render_host(spheres: SphereSet, tree: FlatOctree | None, params: Fra
                                          C.byref(p), C.byref(t), L.fptr(out), counts))
     del keep
     return out, dict(zip(L.COUNT_NAMES, [int(v) for v in counts]))
+
+
+def query_rays_host(spheres: SphereSet, tree: FlatOctree | None, rays, *, layout: int = L.ORT_LAYOUT_COMPACT,
+                    use_octree: bool = True, normals: bool = False):
+    """TEST-ONLY: ``Renderer.trace_rays`` on the host CPU (ort_debug_query_rays: render_core.h
+    query_ray, the kernels' own per-ray function).  Returns (t, sphere[, normals])."""
+    lib = L.analysis_lib()
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    n = rays.shape[0]
+    cr = np.ascontiguousarray(spheres.center_radius, np.float32)
+    if tree is None:
+        keep = ()
+        args = (None, None, None, None, None, 0, None, 0)
+    else:
+        keep = tuple(np.ascontiguousarray(a, t) for a, t in (
+            (tree.node_min, np.float32), (tree.node_max, np.float32), (tree.children_offset, np.int32),
+            (tree.objects_offset, np.int32), (tree.object_count, np.int32), (tree.object_indices, np.int32)))
+        args = (L.fptr(keep[0]), L.fptr(keep[1]), L.iptr(keep[2]), L.iptr(keep[3]), L.iptr(keep[4]),
+                tree.n_nodes, L.iptr(keep[5]), tree.n_indices)
+    rec = np.empty((n, 2), np.int32)
+    nrm = np.zeros((n, 3), np.float32) if normals else None
+    L.acheck(lib.ort_debug_query_rays(L.fptr(cr), spheres.n, *args, int(layout), 1 if use_octree else 0, L.fptr(rays), n,
+                                     rec.ctypes.data_as(C.c_void_p), L.fptr(nrm)))
+    del keep
+    t, sph = np.ascontiguousarray(rec[:, 0]).view(np.float32), np.ascontiguousarray(rec[:, 1])
+    return (t, sph, nrm) if normals else (t, sph)

@@ -1,0 +1,198 @@
+"""The ray set of the ray-query tests (tests/test_ray_query.py, tests/test_gpu_ray_query.py): a
+seeded generator of 3001 rays in six classes for a scene (spheres, tree), the degenerate rays,
+the scenes the tests run on, and the references both suites share (computed once per process).
+
+3001 is neither a multiple of 64 (a wave) nor of a chunk of the persistent walk."""
+import functools
+
+import numpy as np
+
+CLASSES = (("inside", 1200), ("camera", 800), ("axis", 400), ("scaled", 300), ("outside", 200), ("surface", 101))
+N_RAYS = sum(n for _, n in CLASSES)
+assert N_RAYS == 3001
+
+# (spheres, scene seed, tree depth, max spheres per node) and how each is queried
+SCENES = {
+    "compact5": (2000, 7, 5, 1),
+    "compact10": (3000, 11, 10, 1),
+    "compact6": (10000, 42, 6, 0),
+    "explicit": (100, 42, 4, 0),
+    "brute": (100, 42, 4, 0),
+}
+
+
+def class_slices():
+    out, at = {}, 0
+    for name, n in CLASSES:
+        out[name] = slice(at, at + n)
+        at += n
+    return out
+
+
+def _unit(v):
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def make_rays(ort, oracle, s, t, seed):
+    """(3001, 6) float32 rays (origin, direction) for the scene, the classes in CLASSES' order."""
+    rng = np.random.default_rng(seed)
+    lo, hi = t.node_min[0].astype(np.float64), t.node_max[0].astype(np.float64)
+
+    def inside(n):
+        return lo + (hi - lo) * rng.uniform(-0.05, 1.05, (n, 3)), _unit(rng.normal(size=(n, 3)))
+
+    parts = []
+    # 1. inside: origins in (and a little around) the root box, random unit directions
+    parts.append(np.concatenate(inside(1200), axis=1))
+    # 2. camera: from the default camera's origin through uniform points of its image plane
+    cam = oracle.camera(ort.FrameParams.default_camera(320, 180))[:12].astype(np.float64).reshape(4, 3)
+    u, v = rng.uniform(0, 1, (2, 800))
+    d = _unit(cam[1] + u[:, None] * cam[2] + v[:, None] * cam[3] - cam[0])
+    parts.append(np.concatenate([np.broadcast_to(cam[0], (800, 3)), d], axis=1))
+    # 3. axis: one or two direction components exactly +0 or -0, the rest renormalised; a tenth
+    # with the origin of a zero axis exactly on node_min of a random node (NaN slabs)
+    o, d = inside(400)
+    kinds = rng.integers(0, 6, 400)
+    for i, k in enumerate(kinds):
+        axes = [k % 3] if k < 3 else [k % 3, (k + 1) % 3]
+        for a in axes:
+            d[i, a] = -0.0 if rng.random() < 0.5 else 0.0
+        nz = [a for a in range(3) if a not in axes]
+        d[i, nz] /= np.linalg.norm(d[i, nz])
+    for i in np.nonzero(rng.random(400) < 0.1)[0]:
+        a = next(a for a in range(3) if d[i, a] == 0.0)
+        o[i, a] = t.node_min[rng.integers(0, t.n_nodes), a]
+    parts.append(np.concatenate([o, d], axis=1))
+    # 4. scaled: directions of length 10^k, k in -3..3 (most leave the fast walk's range)
+    o, d = inside(300)
+    parts.append(np.concatenate([o, d * 10.0 ** rng.integers(-3, 4, 300)[:, None]], axis=1))
+    # 5. outside: beyond the box's far corner, pointing away
+    o = hi + (hi - lo) * rng.uniform(0.1, 1.0, (200, 3))
+    parts.append(np.concatenate([o, np.abs(rng.normal(size=(200, 3)))], axis=1))
+    # 6. surface: on a random sphere's surface, along +-its normal (t_min = 0.001)
+    k = rng.integers(0, s.n, 101)
+    n = _unit(rng.normal(size=(101, 3)))
+    c, r = s.center_radius[k, :3].astype(np.float64), s.center_radius[k, 3:4].astype(np.float64)
+    parts.append(np.concatenate([c + r * n, n * rng.choice([-1.0, 1.0], 101)[:, None]], axis=1))
+    rays = np.ascontiguousarray(np.concatenate(parts), np.float32)
+    assert rays.shape == (N_RAYS, 6)
+    return rays
+
+
+def degenerate_rays():
+    """12 rays at the edge of what a walk can make sense of: each must terminate and miss.  (The
+    two whose direction is only scaled, by 1e+-20, are proper rays: they start beyond every scene's
+    far corner and point away, so that a miss is the right answer on every scene.)"""
+    inf, nan = np.inf, np.nan
+    o = (0.0, 2.5, -10.0)
+    d = (0.0, 0.0, 1.0)
+    far = (1000.0, 1000.0, 1000.0)
+    rows = [
+        o + (0.0, 0.0, 0.0),
+        o + (inf, 0.0, 1.0),
+        o + (0.0, -inf, 1.0),
+        o + (nan, 0.0, 1.0),
+        o + (0.3, nan, nan),
+        (nan, 2.5, -10.0) + d,
+        (0.0, inf, -10.0) + d,
+        (0.0, 2.5, -inf) + d,
+        o + (0.0, 0.0, 1e-30),
+        far + (0.0, 0.6e20, 0.8e20),
+        far + (0.6e-20, 0.0, 0.8e-20),
+        (inf, -inf, nan) + (nan, inf, -inf),
+    ]
+    with np.errstate(over="ignore"):
+        return np.ascontiguousarray(np.array(rows, np.float64), np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def scene(name):
+    """(spheres, tree, rays) of SCENES[name]; the generator seed is 1000 + depth."""
+    import octreeraytracer_amd as ort
+    from oracle import oracle
+    n, seed, depth, m = SCENES[name]
+    s = ort.random_spheres(n, seed)
+    t = ort.build_octree(s, depth, m)
+    rays = make_rays(ort, oracle, s, t, 1000 + depth)
+    rays.setflags(write=False)
+    return s, t, rays
+
+
+def one_sphere_scene(ort, s, k):
+    one = ort.SphereSet(s.center_radius[k:k + 1].copy(), s.mat_albedo[k:k + 1].copy(), s.fuzz_ri[k:k + 1].copy())
+    return one, ort.build_octree(one, 0, 0)  # a single leaf root
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_hits(name):
+    """The reference records of scene(name)'s rays: (n, 2) int32 {hit, t bits}.  The octree
+    configurations: oracle.trace_rays.  Brute force: over the one-sphere oracle results of every
+    sphere the smallest t, the lowest index attaining it (the shader's test is a strict <); here a
+    third column holds that sphere (-1 none)."""
+    import octreeraytracer_amd as ort
+    from oracle import oracle
+    s, t, rays = scene(name)
+    if name != "brute":
+        ref = oracle.trace_rays(s, t, rays)
+        ref.setflags(write=False)
+        return ref
+    best_t = np.full(len(rays), np.inf, np.float32)
+    best_k = np.full(len(rays), -1, np.int32)
+    for k in range(s.n):
+        one, tree = one_sphere_scene(ort, s, k)
+        r = oracle.trace_rays(one, tree, rays)
+        tk = np.ascontiguousarray(r[:, 1]).view(np.float32)
+        better = (r[:, 0] == 1) & (tk < best_t)
+        best_t[better] = tk[better]
+        best_k[better] = k
+    ref = np.zeros((len(rays), 3), np.int32)
+    ref[:, 0] = best_k >= 0
+    ref[:, 1] = np.where(best_k >= 0, best_t.view(np.int32), 0)
+    ref[:, 2] = best_k
+    ref.setflags(write=False)
+    return ref
+
+
+def check_spheres_against_the_oracle(ort, oracle, s, rays, t_bits, sphere):
+    """Every hit ray, traced by the oracle through the one-sphere scene of the sphere it reports,
+    hits with the same t bits (Sphere_hit returns the same root for a sphere under a tighter
+    t_max whenever it accepts it)."""
+    hit = sphere >= 0
+    assert (sphere[hit] < s.n).all()
+    for k in np.unique(sphere[hit]):
+        sel = np.nonzero(sphere == k)[0]
+        one, tree = one_sphere_scene(ort, s, int(k))
+        r = oracle.trace_rays(one, tree, rays[sel])
+        assert (r[:, 0] == 1).all(), (int(k), sel[r[:, 0] != 1][:5])
+        assert np.array_equal(r[:, 1], t_bits[sel]), (int(k), sel[r[:, 1] != t_bits[sel]][:5])
+
+
+def numpy_normals(s, rays, t, sphere):
+    """IntersectInfo.normal = ((o + t d) - c) / r restated in float32, one rounded operation at
+    a time (the library is built without contraction); zeros for a miss."""
+    f = np.float32
+    o, d = rays[:, :3].astype(f), rays[:, 3:].astype(f)
+    out = np.zeros((len(rays), 3), f)
+    hit = sphere >= 0
+    k = sphere[hit]
+    c, r = s.center_radius[k, :3].astype(f), s.center_radius[k, 3:4].astype(f)
+    with np.errstate(all="ignore"):
+        prod = (t[hit, None].astype(f) * d[hit]).astype(f)
+        p = (o[hit] + prod).astype(f)
+        out[hit] = ((p - c).astype(f) / r).astype(f)
+    return out
+
+
+def hit_shares(hit):
+    """Overall and per-class hit shares of a 3001-ray result."""
+    sl = class_slices()
+    return float(hit.mean()), {name: float(hit[sl[name]].mean()) for name in sl}
+
+
+def assert_hit_floors(hit):
+    """The floors a kernel that misses everything cannot pass (measured on the reference: overall
+    0.15-0.36, every class but 'outside' 0.096-0.634, 'outside' 0)."""
+    overall, per = hit_shares(hit)
+    assert overall >= 0.10, overall
+    assert per["inside"] >= 0.10 and per["surface"] >= 0.10, per
+    assert per["outside"] == 0.0, per

@@ -1,4 +1,4 @@
-"""Per-kernel VGPR / spill / occupancy table of ort_kernel.hip from the compiler's
+"""Per-kernel VGPR / spill / scratch / static-LDS / occupancy table of ort_kernel.hip from the compiler's
 kernel-resource-usage remarks (no GPU needed).
 usage: python tools/kernel_resources.py [filter-substring] [-- extra hipcc flags]"""
 import re
@@ -24,7 +24,8 @@ for line in err.splitlines():
         cur = {"name": m.group(1)}
         rows.append(cur)
         continue
-    m = re.search(r"remark:\s+(VGPRs|AGPRs|SGPRs|VGPRs Spill|SGPRs Spill|Occupancy \[waves/SIMD\]|ScratchSize \[bytes/lane\]):"
+    m = re.search(r"remark:\s+(VGPRs|AGPRs|SGPRs|VGPRs Spill|SGPRs Spill|Occupancy \[waves/SIMD\]|ScratchSize \[bytes/lane\]|"
+                  r"TotalSGPRs|LDS Size \[bytes/block\]):"
                   r" (\d+)", line)
     if m and cur is not None:
         cur[m.group(1)] = int(m.group(2))
@@ -37,10 +38,11 @@ def demangle(n):
         return n
 
 
-print(f"{'kernel':70s} {'VGPR':>5s} {'SGPR':>5s} {'vspill':>6s} {'sspill':>6s} {'occ':>4s}")
+print(f"{'kernel':70s} {'VGPR':>5s} {'SGPR':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'LDS':>6s} {'occ':>4s}")
 for r in rows:
     d = demangle(r["name"]).replace("(anonymous namespace)::", "").split("(")[0]
     if flt and flt not in d:
         continue
-    print(f"{d[:70]:70s} {r.get('VGPRs', -1):5d} {r.get('SGPRs', -1):5d} {r.get('VGPRs Spill', 0):6d} "
-          f"{r.get('SGPRs Spill', 0):6d} {r.get('Occupancy [waves/SIMD]', -1):4d}")
+    print(f"{d[:70]:70s} {r.get('VGPRs', -1):5d} {r.get('SGPRs', r.get('TotalSGPRs', -1)):5d} {r.get('VGPRs Spill', 0):6d} "
+          f"{r.get('SGPRs Spill', 0):6d} {r.get('ScratchSize [bytes/lane]', 0):7d} {r.get('LDS Size [bytes/block]', 0):6d} "
+          f"{r.get('Occupancy [waves/SIMD]', -1):4d}")
