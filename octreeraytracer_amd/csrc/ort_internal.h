@@ -88,4 +88,14 @@ int64_t ort_debug_walk_steps(const float* sphere_center_radius, const float* sph
                              const int32_t* object_count, int32_t n_nodes, const int32_t* object_indices,
                              int64_t n_indices, const ort_params* params, int32_t block_step, int32_t* lens,
                              int64_t n_lens, uint16_t* steps, int64_t cap);
+// TEST-ONLY: the image a workgroup copies into LDS for a tree of this depth (render_core.h
+// lds_layout: what k_lds_image writes, by the same fill_fast_planes), built on the host from the
+// forward plane tables planes[3 (2^depth + 1)].  layout[7] = {image bytes, rank LUT offset,
+// plane table bytes, pop table 1 offset (-1: none), pop table 2 offset, entries per pop table,
+// Masks64::kPopTable of this build}; image: NULL, or cap_words 32-bit words to receive it.
+int ort_debug_lds_image(int32_t depth, const float* planes, uint32_t* image, int64_t cap_words, int32_t* layout);
+// TEST-ONLY: how often the host's depth <= 8 camera walks (fast_pop, inline leaf children) popped
+// mask bit hb = 8 L + 7 - rank (hb_pops[64]) and under which direction-sign mask m
+// (sign_masks[8], counted per pop) since the last reset; reset != 0 clears the counts.
+int ort_debug_pop_coverage(uint64_t* hb_pops, uint64_t* sign_masks, int32_t reset);
 }

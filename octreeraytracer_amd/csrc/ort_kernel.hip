@@ -4153,6 +4153,39 @@ int64_t ort_debug_walk_steps(const float* cr, const float* ma, const float* fr, 
     }
 }
 
+int ort_debug_lds_image(int32_t depth, const float* planes, uint32_t* image, int64_t cap_words, int32_t* layout) {
+    if (depth < 0 || depth > ORT_COMPACT_MAX_DEPTH || !planes || !layout)
+        return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_lds_image: bad argument");
+    const bool rev = ort::fast_rev_planes(depth);
+    const ort::LdsLayout l = ort::lds_layout(depth, rev);
+    layout[0] = l.frames;
+    layout[1] = l.lut;
+    layout[2] = 4 * ort::fast_plane_floats(depth, rev);
+    layout[3] = l.pop;
+    layout[4] = l.pop < 0 ? -1 : l.pop + ort::kPopTable2;
+    layout[5] = l.pop < 0 ? 0 : ort::kPopEntries;
+    layout[6] = ort::Masks64::kPopTable ? 1 : 0;
+    if (!image) return ORT_OK;
+    if (cap_words * 4 < (int64_t)l.frames) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_lds_image: image too small");
+    // what k_lds_image writes: the tables (fill_fast_planes), then the rank LUT
+    std::vector<float> img((size_t)l.frames / 4, 0.0f);
+    ort::fill_fast_planes(planes, img.data(), depth, rev);
+    uint8_t* lut = reinterpret_cast<uint8_t*>(img.data()) + l.lut;
+    for (int i = 0; i < (int)kRankLutBytes; ++i) lut[i] = ort::rank_lut_entry((uint32_t)i >> 8, (uint32_t)i & 255u);
+    std::memcpy(image, img.data(), (size_t)l.frames);
+    return ORT_OK;
+}
+
+int ort_debug_pop_coverage(uint64_t* hb_pops, uint64_t* sign_masks, int32_t reset) {
+    for (int i = 0; i < 64; ++i)
+        if (hb_pops) hb_pops[i] = ort::g_pop_cover[i];
+    for (int i = 0; i < 8; ++i)
+        if (sign_masks) sign_masks[i] = ort::g_pop_cover[64 + i];
+    if (reset)
+        for (int i = 0; i < 72; ++i) ort::g_pop_cover[i] = 0;
+    return ORT_OK;
+}
+
 #endif  // ORT_ANALYSIS
 
 }  // extern "C"

@@ -270,14 +270,47 @@ ORT_FN int fast_plane_floats(int depth, bool rev) {
     return rev ? 7 * fast_rev_T(depth) + (1 << depth) + 1 : 3 * fast_axis_floats(depth, false);
 }
 ORT_FN int fast_plane_floats(int depth) { return fast_plane_floats(depth, fast_rev_planes(depth)); }
+// The pop table of the depth <= 8 image (the camera walk's fast_pop, Masks64::kPopTable): what
+// the pop derives from (hb, D) alone, hb = 8L + 7 - rank the popped mask bit, once per scene
+// instead of per lane and step.  Two tables of kPopEntries 16-byte entries, entry hb at
+// kPopTableOff + 16 hb in the axis-0 block and kPopTable2 bytes further (the same place of the
+// axis-1 block): the tail of the gap after each block's reversed table, which ends at byte
+// 4 (T + 2^D + 1) <= 2052, so the image keeps its size and every other byte.  The camera walk
+// never pops a level-D leaf (kInlineLeaves), so hb < 8 (D - 1) <= 56; the entries from there
+// on are zero.  For a level-(L+1) child of width w4 = 4 << (D-1-L) bytes of plane table:
+//   table 1: { m8 = ~(2 w4 - 1), bitA << s, bitB << s, bitC << s },  s = log2 w4, the rank's
+//            bit per role axis (A: rank bit 1, B: bit 0, C: bit 2) -- near = (near & m8) | bit << s
+//   table 2: { w4, w4 / 2, low word of 1 << hb, high word of 1 << hb }
+constexpr int kPopEntries = 56;
+constexpr int kPopTableOff = 12 * 256 - 16 * kPopEntries;  // 2176
+constexpr int kPopTable2 = 12 * 256;
+static_assert(kPopTableOff % 16 == 0 && kPopTableOff >= 4 * (2 * 256 + 1), "the pop table overlaps the reversed table");
+ORT_FN bool fast_pop_table(int depth, bool rev) { return rev && depth <= 8; }
+ORT_FN uint32_t pop_table_word(int depth, int table, int hb, int k) {
+    const int L = hb >> 3;
+    if (hb >= 8 * (depth - 1)) return 0u;
+    const uint32_t rk = (uint32_t)(~hb) & 7u;
+    const uint32_t s = (uint32_t)(depth + 1 - L);
+    const uint32_t w4 = 1u << s;
+    if (table == 0) {
+        if (k == 0) return ~(2u * w4 - 1u);
+        const uint32_t bit = k == 1 ? (rk >> 1) & 1u : (k == 2 ? rk & 1u : (rk >> 2) & 1u);
+        return bit << s;
+    }
+    if (k == 0) return w4;
+    if (k == 1) return w4 >> 1;
+    return (uint32_t)(((uint64_t)1 << hb) >> (k == 2 ? 0 : 32));
+}
 struct LdsLayout {
     int lut;     // byte offset of the rank LUT
     int frames;  // byte offset of the frame columns (= the image's size; a multiple of 16)
+    int pop;     // byte offset of the pop table (the second one kPopTable2 further); -1: none
 };
 ORT_FN LdsLayout lds_layout(int depth, bool rev) {
     const int pb = (4 * fast_plane_floats(depth, rev) + 15) & ~15;
     const int T = fast_rev_T(depth);
     LdsLayout l;
+    l.pop = fast_pop_table(depth, rev) ? kPopTableOff : -1;
     if (rev && 4 * (2 * T - (1 << depth) - 1) >= 2048) {  // the gap after axis 0's reversed table
         l.lut = 12 * T - 2048;
         l.frames = pb;
@@ -292,12 +325,18 @@ ORT_FN void fill_fast_planes(const float* fwd, float* out, int depth, bool rev, 
     const int S = fast_axis_floats(depth, rev);
     const int T = fast_rev_T(depth);
     const int n = fast_plane_floats(depth, rev);
+    const bool pop = fast_pop_table(depth, rev);
     for (int o = i0; o < n; o += step) {  // gather form: one writer per entry
         const int a = o / S, r = o - a * S;
-        float v = 0.0f;  // the gaps: never read as planes
-        if (r < P1) v = fwd[a * P1 + r];
-        else if (rev && r >= T && r - T < P1) v = fwd[a * P1 + (P1 - 1 - (r - T))];
-        out[o] = v;
+        uint32_t u = 0u;  // the gaps: never read as planes
+        if (r < P1) u = f2u(fwd[a * P1 + r]);
+        else if (rev && r >= T && r - T < P1) u = f2u(fwd[a * P1 + (P1 - 1 - (r - T))]);
+        else if (pop && a < 2 && 4 * r >= kPopTableOff) {  // the pop tables, in the gaps of axes 0 and 1
+            const int i = r - kPopTableOff / 4;
+            u = pop_table_word(depth, a, i >> 2, i & 3);
+        }
+        // stored as an integer word: several table words are NaN bit patterns
+        __builtin_memcpy(out + o, &u, 4);
     }
 }
 ORT_FN void fill_fast_planes(const float* fwd, float* out, int depth) {
@@ -722,6 +761,15 @@ struct Masks64 {  // levels 0..7: trees of depth <= 8
 #define ORT_KID_SKIP_CAMERA8 0
 #endif
     static constexpr bool kKidSkip = ORT_KID_SKIP_CAMERA8;
+    // the pop's level arithmetic read from the image's pop tables (lds_layout) instead of
+    // computed per lane and step (fast_pop); 0: the ALU pop.  Needs kInlineLeaves: the tables
+    // have no entries for level-D leaves.  (C3 frame 1.645 -> 1.520 ms in interleaved A/B; with
+    // table 1 alone, the widths and the bit's mask still computed, 1.551 ms: dropped.)
+#ifndef ORT_POP_TABLE
+#define ORT_POP_TABLE 1
+#endif
+    static constexpr bool kPopTable = ORT_POP_TABLE;
+    static_assert(!kPopTable || kInlineLeaves, "the pop table has no level-D entries");
     uint64_t m;
     ORT_FN void clear() { m = 0; }
     ORT_FN bool empty() const { return m == 0; }
@@ -731,6 +779,9 @@ struct Masks64 {  // levels 0..7: trees of depth <= 8
         m ^= (uint64_t)1 << hb;
         return hb;
     }
+    // (kPopTable) pop() in two halves: the bit's index, then its mask from the table
+    ORT_FN int peek() const { return 63 - __builtin_clzll(m); }
+    ORT_FN void drop(uint32_t lo, uint32_t hi) { m ^= ((uint64_t)hi << 32) | lo; }
     // clears bit hb (= 8L + 7 - rank) and returns whether it was set
     ORT_FN bool take(int hb) {
         const uint64_t b = (uint64_t)1 << hb;
@@ -765,6 +816,7 @@ struct Masks96 {  // levels 0..9 (ORT_COMPACT_MAX_DEPTH 10)
 #endif
     static constexpr bool kLeadLeaves = ORT_LEAD_LEAVES_DEEP;
     static constexpr bool kRevPlanes = false;
+    static constexpr bool kPopTable = false;  // (the depth <= 8 image's: Masks64)
     static constexpr bool kKeepNear = true;
     // the rejected-sphere skip here too: with the kid entry loaded in the pop, C5's camera
     // walk 17.52 -> 16.41 ms in A/B (no gain while the entry was loaded in the node's step)
@@ -840,8 +892,15 @@ struct FastStateT {
     static ORT_FN uint32_t table_base(const float* planes) {
         return (uint32_t)(size_t)(const __attribute__((address_space(3))) float*)planes;
     }
+    // a 16-byte pop table entry (lds_layout), addressed like a plane
+    ORT_FN uint4 entry(uint32_t a) const { return *(const __attribute__((address_space(3))) uint4*)(size_t)a; }
 #else
     ORT_FN float plane(uint32_t off) const { return *(const float*)((const char*)pl0 + off); }
+    ORT_FN uint4 entry(uint32_t off) const {
+        uint4 e;
+        __builtin_memcpy(&e, (const char*)pl0 + off, 16);
+        return e;
+    }
     static ORT_FN uint32_t table_base(const float*) { return 0u; }
 #endif
     // otherwise: the ray-order plane table of each role axis, plane(i) = *(pA + sA * i bytes)
@@ -916,6 +975,7 @@ struct Masks96Lean : Masks96 {
 // (inline leaves pay off on coherent camera rays, not on scattered bounce rays).
 struct Masks64Plain : Masks64 {
     static constexpr bool kInlineLeaves = false;
+    static constexpr bool kPopTable = false;  // pops level-D leaves, which the table does not hold
     static constexpr bool kPreMid = false;
     static constexpr bool kKidSkip = true;
 };
@@ -1251,6 +1311,12 @@ ORT_FN bool fast_visit(const KScene& S, const uint8_t* rank_lut, FastStateT<Mask
     return false;
 }
 
+#if ORT_ANALYSIS
+// analysis library, host walks only (ort_debug_pop_coverage): how often the depth <= 8 camera
+// walk popped mask bit hb ([hb]) and under which direction-sign mask m ([64 + m])
+inline unsigned long long g_pop_cover[72];
+#endif
+
 // Pop the next node -- the lowest remaining rank of the deepest level with one left (the masks
 // must not be empty) -- and load its record and box planes.
 template <bool COUNT, class Masks, class Frames>
@@ -1282,24 +1348,48 @@ template <bool COUNT, class Masks, class Frames>
 ORT_FN void fast_pop(const KScene& S, FastStateT<Masks>& st, Frames& fr) {
     const int D = S.depth;
     // next node: lowest remaining rank of the deepest level with one left
-    const int hb = st.masks.pop();
+    static_assert(!Masks::kPopTable || (Masks::kRevPlanes && Masks::kInlineLeaves), "pop table: depth <= 8 camera walk");
+    int hb;
+    if constexpr (Masks::kPopTable) hb = st.masks.peek();  // (the bit is cleared with the table's mask below)
+    else hb = st.masks.pop();
     const int L = hb >> 3;
     const uint32_t rk = (uint32_t)(~hb) & 7u;
     const int w = 1 << (D - 1 - L);  // child width in plane steps
     st.depth = L + 1;
     st.node = fr.getCo(L) + (int)((st.otab >> (4 * rk)) & 15u);
     fetch_rec(S, st.node, kKidPrefetch && !COUNT && Masks::kKidSkip && S.kid, st);
+#if ORT_ANALYSIS && !defined(__HIP_DEVICE_COMPILE__)
+    if (Masks::kInlineLeaves && Masks::kRevPlanes) {  // ort_debug_pop_coverage: the camera walk's pops
+        g_pop_cover[hb & 63] += 1;
+        g_pop_cover[64 + (st.otab & 7u)] += 1;
+    }
+#endif
     if (Masks::kRevPlanes) {
         // near plane of the level-(L+1) child: the level-L ancestor's (offset bits below 8w
         // cleared; the table start is a multiple of 4T >= 8w bytes) plus w planes on the axes
         // where the child is the far half
-        const uint32_t w4 = 4u << (D - 1 - L);
-        st.h4 = w4 >> 1;
-        const uint32_t m8 = ~(2u * w4 - 1u);
-        const uint32_t s = (uint32_t)(D + 1 - L);  // log2(w4)
-        st.aA = (st.aA & m8) | (((rk >> 1) & 1u) << s);
-        st.aB = (st.aB & m8) | ((rk & 1u) << s);
-        st.aC = (st.aC & m8) | (((rk >> 2) & 1u) << s);
+        uint32_t w4;
+        if constexpr (Masks::kPopTable) {
+            // the image's pop tables (lds_layout), two 16-byte reads: m8 and the three offsets;
+            // the widths and the popped bit's mask
+            const uint32_t ta = FastStateT<Masks>::table_base(st.pl0) + (uint32_t)kPopTableOff + 16u * (uint32_t)hb;
+            const uint4 e = st.entry(ta);
+            st.aA = (st.aA & e.x) | e.y;
+            st.aB = (st.aB & e.x) | e.z;
+            st.aC = (st.aC & e.x) | e.w;
+            const uint4 e2 = st.entry(ta + (uint32_t)kPopTable2);
+            w4 = e2.x;
+            st.h4 = e2.y;
+            st.masks.drop(e2.z, e2.w);
+        } else {
+            w4 = 4u << (D - 1 - L);
+            st.h4 = w4 >> 1;
+            const uint32_t m8 = ~(2u * w4 - 1u);
+            const uint32_t s = (uint32_t)(D + 1 - L);  // log2(w4)
+            st.aA = (st.aA & m8) | (((rk >> 1) & 1u) << s);
+            st.aB = (st.aB & m8) | ((rk & 1u) << s);
+            st.aC = (st.aC & m8) | (((rk >> 2) & 1u) << s);
+        }
         st.tNA = st.iA * (st.plane(st.aA) - st.oA);
         st.tFA = st.iA * (st.plane(st.aA + w4) - st.oA);
         st.tNB = st.iB * (st.plane(st.aB) - st.oB);

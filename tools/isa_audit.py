@@ -18,11 +18,15 @@ from collections import defaultdict
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
-want = sys.argv[1] if len(sys.argv) > 1 else "ort_trace_pairILb0ELi1E"
+args, extra = sys.argv[1:], []
+if "--" in args:  # [kernel-substring] -- extra hipcc flags (a variant's -D...)
+    i = args.index("--")
+    args, extra = args[:i], args[i + 1:]
+want = args[0] if args else "ort_trace_pairILb0ELi1E"
 asm = "/tmp/_ort_isa_audit.s"
 subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
                 "-fno-fast-math", "-fno-slp-vectorize", "-fPIC", "-Wno-unused-parameter", "--cuda-device-only", "-S",
-                str(ROOT / "octreeraytracer_amd/csrc/ort_kernel.hip"), "-o", asm], check=True, capture_output=True)
+                str(ROOT / "octreeraytracer_amd/csrc/ort_kernel.hip"), "-o", asm] + extra, check=True, capture_output=True)
 text = open(asm).read()
 names = [n for n in re.findall(r"^(_Z\S+):", text, re.M) if want in n]
 if not names:
