@@ -45,7 +45,15 @@ extern "C" {
 typedef struct ort_ctx ort_ctx;
 
 /* The shader's uniforms (glsl:13-18, 48-53).  view is column-major like glm::mat4
- * (view[4*col + row]); model/projection are unused by the reference shader. */
+ * (view[4*col + row]); model/projection are unused by the reference shader.
+ *
+ * num_samples must be at least 1: every call that renders (ort_render, ort_render_ex,
+ * ort_count_traffic, ort_group_submit[_fmt], ort_group_render[_fmt]) refuses a smaller value with
+ * ORT_ERR_INVALID_ARG "num_samples must be at least 1" before anything is allocated or launched,
+ * and leaves the output untouched.  (The shader divides the sum of zero samples by zero -- a
+ * frame of NaN -- and gives a frame of +0 for a negative count; neither is of use to a caller.)
+ * max_depth <= 0 is a frame: radiance() returns (1, 1, 1) without tracing a ray, so every
+ * channel of every pixel is 1.0 (255 in ORT_FORMAT_RGBA8), whatever the scene. */
 typedef struct ort_params {
     int32_t width, height;      /* iResolution.xy of the FULL frame (src/raytracer.cpp:150) */
     int32_t num_samples;        /* numSamples (src/config.h:20) */

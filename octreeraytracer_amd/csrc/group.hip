@@ -443,6 +443,8 @@ int ort_group_submit_fmt(ort_group* g, const ort_params* p, void* rgb_out, int32
         return gfail(g, ORT_ERR_INVALID_ARG, "ort_group_submit: format: unknown ORT_FORMAT_*");
     const size_t wpp = format == ORT_FORMAT_RGBA8 ? 1 : 3;  // 32-bit words per pixel
     if (p->width <= 0 || p->height <= 0) return gfail(g, ORT_ERR_INVALID_ARG, "ort_group_submit: width/height must be positive");
+    // (as ort_render's check_params, here before any rank has rendered or a buffer has grown)
+    if (p->num_samples < 1) return gfail(g, ORT_ERR_INVALID_ARG, "ort_group_submit: num_samples must be at least 1");
     const int W = p->width, H = p->height, N = g->n;
     const long long tk = g->next_ticket;
     GroupSlot& S = g->slot[(size_t)(tk % (long long)g->slot.size())];

@@ -2309,13 +2309,24 @@ ort::KCamera to_kcamera(const ort::CameraFrame& f) {
     return k;
 }
 
-std::string check_params(const ort_params* p, const ort_tile* t) {
+// "" or what is wrong with the frame's size and the tile: what the host emulation checks too (it
+// restates the shader, which defines a frame for every sample count).
+std::string check_frame_tile(const ort_params* p, const ort_tile* t) {
     if (!p || !t) return "null params or tile";
     if (p->width <= 0 || p->height <= 0) return "width/height must be positive";
     if (t->width < 0 || t->rows < 0) return "negative tile size";
     if (t->x0 < 0 || (int64_t)t->x0 + t->width > p->width) return "tile columns outside the frame";
     if (t->y0 < 0) return "negative y0";
     if (t->band_height > 0 && t->band_stride < t->band_height) return "band_stride < band_height";
+    return "";
+}
+
+// ... and with the frame's parameters, for the calls that render on the device (include/ort.h
+// ort_params): no samples would leave the output unwritten or finalize stale sums.
+std::string check_params(const ort_params* p, const ort_tile* t) {
+    const std::string bad = check_frame_tile(p, t);
+    if (!bad.empty()) return bad;
+    if (p->num_samples < 1) return "num_samples must be at least 1";
     return "";
 }
 
@@ -3549,6 +3560,8 @@ int ort_frame_trace_times_ms(ort_ctx* ctx, int n, float* ms, int32_t* launches) 
 
 int ort_count_traffic(ort_ctx* ctx, const ort_params* params, const ort_tile* tile, uint64_t* counts) {
     if (!ctx || !counts) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_count_traffic: null argument");
+    const std::string bad = check_params(params, tile);  // before the counters and the frame are allocated
+    if (!bad.empty()) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_count_traffic: " + bad);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!ctx->counters.p) {
         HIPCHK(ctx, hipMalloc(&ctx->counters.p, 64));
@@ -3732,7 +3745,7 @@ int ort_debug_emulate_render(const float* cr, const float* ma, const float* fr, 
                              const int32_t* cnt, int32_t n_nodes, const int32_t* idx, int64_t n_indices,
                              int32_t layout, const ort_params* p, const ort_tile* t, float* out, uint64_t* counts) {
     try {
-        const std::string bad = check_params(p, t);
+        const std::string bad = check_frame_tile(p, t);
         if (!bad.empty()) return fail(nullptr, ORT_ERR_INVALID_ARG, bad);
         ort::SceneInput in{cr, ma, fr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices};
         const std::string vbad = ort::validateScene(in);

@@ -64,6 +64,9 @@ def inputs(ort, c):
     elif c["scene"] == "twins":  # n seeded spheres and barely overlapping copies of the last k
         from test_gpu_explicit import twins
         s = twins(c["n"], 42, c["k"], c["gap"])
+    elif c["scene"] == "chart":  # tests/chart_scenes.py: the material chart
+        from chart_scenes import chart
+        s = chart(ort)
     else:
         s = ort.debug_spheres()
     t = ort.build_octree(s, c["depth"], c["m"])
@@ -170,7 +173,8 @@ def test_fixtures_regenerate_bit_for_bit(name):
 
 @pytest.mark.skipif(not REGENERATE, reason="needs oracle/_ref/glsl_run and the reference's shaders")
 @pytest.mark.parametrize("name", ["c1", "prebuilt_spp4_d8", "c2_spp2_d4", "m8_d7_odd_b2", "debug_pose", "c2tree_zoom1",
-                                  "config_default", "explicit_d11_twins_b3", "explicit_d13_twins"])
+                                  "config_default", "explicit_d11_twins_b3", "explicit_d13_twins", "chart_spp2_b8",
+                                  "chart_odd_spp5_b6", "chart_md0_spp3"])
 def test_canonical_hashes_regenerate(name):
     """The canonical-builtin hashes are what the reference's shaders give now."""
     import sys

@@ -28,6 +28,9 @@ def scene(ort, name):
         return ort.debug_spheres()
     if name == "prebuilt":
         return ort.prebuilt_spheres()
+    if name == "chart":  # tests/chart_scenes.py: a negative radius, concentric and identical spheres
+        from chart_scenes import chart
+        return chart(ort)
     return ort.random_spheres(int(name.replace("rand", "").replace("k", "000")), 42)
 
 

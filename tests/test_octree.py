@@ -24,6 +24,9 @@ def scene(ort, name):
         return ort.debug_spheres()
     if name == "prebuilt":
         return ort.prebuilt_spheres()
+    if name == "chart":  # tests/chart_scenes.py: a negative radius, concentric and identical spheres
+        from chart_scenes import chart
+        return chart(ort)
     return ort.random_spheres(int(name.replace("rand", "").replace("k", "000")), 42)
 
 
@@ -41,7 +44,7 @@ def test_builder_matches_reference_fixture(ort, key):
     assert np.array_equal(t.object_indices, fx["indices"]), key
 
 
-@pytest.mark.parametrize("key", ["rand10k_d6_m0", "rand10k_d6_m1"])
+@pytest.mark.parametrize("key", ["rand10k_d6_m0", "rand10k_d6_m1", "chart_d6_m0"])
 def test_builder_matches_reference_hash(ort, key):
     name, d, m = parse_key(key)
     t = ort.build_octree(scene(ort, name), d, m)

@@ -71,6 +71,7 @@ CASES = {
 
 # --canonical only (hashes of whole frames): the bench's C2 and C3 frames (bench.py checks its own frame
 # against them); C2 at 4 samples and 8 bounces
+CHART = dict(scene="chart", n=30, dyaw=180.0, dpitch=0.0, pos=[0.0, 3.5, -8.0])
 CANON_EXTRA = {
     "c2_full": dict(scene="random", n=10000, depth=6, m=0, W=1920, H=1080, spp=1, md=1, oct=1, dyaw=0.0, dpitch=0.0),
     "c3_full": dict(scene="random", n=100000, depth=8, m=0, W=3840, H=2160, spp=1, md=1, oct=1, dyaw=0.0, dpitch=0.0),
@@ -136,6 +137,17 @@ CANON_EXTRA = {
                                   oct=1, dyaw=0.0, dpitch=0.0),
     "explicit_d13_twins": dict(scene="twins", n=100, k=8, gap=1.999, depth=13, m=1, W=320, H=180, spp=1, md=2, oct=1,
                                dyaw=0.0, dpitch=0.0),
+    # --- the material chart (tests/chart_scenes.py): fuzz >= 1, albedo > 1 and 0, refraction index <= 1
+    # and 2.4, a negative radius, material codes outside {0, 1, 2}, nested and identical spheres, from
+    # the chart's own camera ((0, 3.5, -8) looking toward -z); its two trees (105 and 181,769 nodes),
+    # brute force, an odd frame size, and a frame without bounces (maxDepth 0: every channel 1)
+    "chart_b1": dict(CHART, depth=4, m=1, W=96, H=64, spp=1, md=1, oct=1),
+    "chart_spp2_b8": dict(CHART, depth=4, m=1, W=96, H=64, spp=2, md=8, oct=1),
+    "chart_odd_spp5_b6": dict(CHART, depth=4, m=1, W=97, H=63, spp=5, md=6, oct=1),
+    "chart_d6m0_spp2_b4": dict(CHART, depth=6, m=0, W=96, H=64, spp=2, md=4, oct=1),
+    "chart_brute_spp2_b6": dict(CHART, depth=4, m=1, W=64, H=48, spp=2, md=6, oct=0),
+    "chart_spp7_b3": dict(CHART, depth=4, m=1, W=48, H=32, spp=7, md=3, oct=1),
+    "chart_md0_spp3": dict(CHART, depth=4, m=1, W=48, H=32, spp=3, md=0, oct=1),
 }
 PRELUDE = ROOT / "oracle" / "glsl_canonical_builtins.glsl"
 
@@ -159,6 +171,10 @@ def case_inputs(c):
         sys.path.insert(0, str(ROOT / "tests"))
         from test_gpu_explicit import twins
         s = twins(c["n"], 42, c["k"], c["gap"])
+    elif c["scene"] == "chart":
+        sys.path.insert(0, str(ROOT / "tests"))
+        from chart_scenes import chart
+        s = chart(ort)
     else:
         s = ort.debug_spheres()
     t = ort.build_octree(s, c["depth"], c["m"])

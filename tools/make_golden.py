@@ -8,6 +8,7 @@ from the CPU oracle (oracle/ort_oracle.c) and pin it against regressions; they a
 reference outputs (the reference never reads pixels back).
 
 usage: python tools/make_golden.py [--large]
+       python tools/make_golden.py --trees chart_d4_m1 chart_d6_m0   (only these entries of the manifest)
 """
 from __future__ import annotations
 
@@ -40,22 +41,51 @@ def scene(name):
         return ort.debug_spheres()
     if name == "prebuilt":
         return ort.prebuilt_spheres()
+    if name == "chart":  # tests/chart_scenes.py
+        sys.path.insert(0, str(ROOT / "tests"))
+        from chart_scenes import chart
+        return chart(ort)
     n = int(name.replace("rand", "").replace("k", "000"))
     return ort.random_spheres(n, 42)
 
 
 SMALL_TREES = [("debug", 3, 2), ("prebuilt", 5, 1), ("prebuilt", 3, 0), ("rand100", 3, 0), ("rand100", 4, 0),
-               ("rand1000", 5, 1), ("rand1000", 4, 0)]
-LARGE_TREES = [("rand10k", 6, 0), ("rand10k", 6, 1), ("rand100k", 8, 0), ("rand100k", 8, 1)]
+               ("rand1000", 5, 1), ("rand1000", 4, 0), ("chart", 4, 1)]
+LARGE_TREES = [("rand10k", 6, 0), ("rand10k", 6, 1), ("chart", 6, 0), ("rand100k", 8, 0), ("rand100k", 8, 1)]
+
+
+def tree_entry(name, d, m):
+    """The manifest entry of a tree from the reference builder (a small one's fixture is written)."""
+    s = scene(name)
+    rec, idx, secs = oracle.ref_build_octree(s.center_radius, d, m)
+    key = f"{name}_d{d}_m{m}"
+    entry = {"nodes": int(rec.shape[0]), "indices": int(idx.shape[0]), "sha256": sha(rec, idx),
+             "reference_build_seconds": secs}
+    if (name, d, m) in SMALL_TREES:
+        np.savez(G / f"octree_{key}.npz", records=rec, indices=idx)
+        entry["file"] = f"octree_{key}.npz"
+    print(key, entry["nodes"], entry["indices"])
+    return key, entry
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--large", action="store_true", help="also hash the 100k-sphere trees (slow)")
+    ap.add_argument("--trees", nargs="+", metavar="KEY", help="update only these tree entries (name_dD_mM) of "
+                    "the manifest, every other entry left as it is")
     args = ap.parse_args()
     if not oracle.ref_octree_available():
         raise SystemExit("oracle/_ref/ref_octree missing: build with `make ref` (needs /root/reference)")
     G.mkdir(parents=True, exist_ok=True)
+    if args.trees:
+        manifest = json.loads((G / "manifest.json").read_text())
+        for key in args.trees:
+            name, d, m = key.split("_")
+            if (name, int(d[1:]), int(m[1:])) not in SMALL_TREES + LARGE_TREES:
+                raise SystemExit(f"{key}: not in SMALL_TREES or LARGE_TREES")
+            manifest["trees"].update([tree_entry(name, int(d[1:]), int(m[1:]))])
+        (G / "manifest.json").write_text(json.dumps(manifest, indent=1))
+        return
     manifest = {"generator": "tools/make_golden.py", "spheres": {}, "trees": {}, "images": {}}
 
     for name in ("rand100", "rand1000", "rand10k", "rand100k"):
@@ -66,17 +96,8 @@ def main():
     np.savez(G / "spheres_rand100_seed42.npz", center_radius=s.center_radius, mat_albedo=s.mat_albedo,
              fuzz_ri=s.fuzz_ri)
 
-    for name, d, m in SMALL_TREES + (LARGE_TREES if args.large else LARGE_TREES[:2]):
-        s = scene(name)
-        rec, idx, secs = oracle.ref_build_octree(s.center_radius, d, m)
-        key = f"{name}_d{d}_m{m}"
-        entry = {"nodes": int(rec.shape[0]), "indices": int(idx.shape[0]), "sha256": sha(rec, idx),
-                 "reference_build_seconds": secs}
-        if (name, d, m) in SMALL_TREES:
-            np.savez(G / f"octree_{key}.npz", records=rec, indices=idx)
-            entry["file"] = f"octree_{key}.npz"
-        manifest["trees"][key] = entry
-        print(key, entry["nodes"], entry["indices"])
+    for name, d, m in SMALL_TREES + (LARGE_TREES if args.large else LARGE_TREES[:3]):
+        manifest["trees"].update([tree_entry(name, d, m)])
 
     # oracle images (regression pins of the restatement)
     s = scene("rand100")
