@@ -12,7 +12,7 @@ HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -ffp-contract=off -fno-fast-ma
 HOST_SRCS := octree.cpp scene.cpp host_abi.cpp layout.cpp raytracer.cpp
 HOST_OBJS := $(addprefix $(OBJ)/,$(HOST_SRCS:.cpp=.o))
 HIP_OBJS := $(OBJ)/ort_kernel.o $(OBJ)/gpu_build.o $(OBJ)/group.o
-HDRS := $(wildcard $(SRC)/*.h) $(SRC)/prebuilt_scene.inc $(SRC)/ray_query.inc include/ort.h include/ort_math.h
+HDRS := $(wildcard $(SRC)/*.h) $(SRC)/prebuilt_scene.inc $(SRC)/ray_query.inc $(SRC)/accum.inc include/ort.h include/ort_math.h
 
 # The analysis library (test/analysis surface: ort_debug_* host emulation and walk statistics,
 # ORT_OPT_DEBUG_FLAGS) -- the same sources with -DORT_ANALYSIS=1; the CPU suite and tools/
@@ -55,7 +55,10 @@ $(LIB): $(HOST_OBJS) $(HIP_OBJS)
 	@mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -ldl -Wl,-soname,libort.so
 
-examples: build/ort_main build/stats_row build/trace_rays
+examples: build/ort_main build/stats_row build/trace_rays build/progressive
+
+build/progressive: tests/cpp/progressive.cpp $(LIB) $(HDRS)
+	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ tests/cpp/progressive.cpp -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
 
 build/trace_rays: tests/cpp/trace_rays.cpp $(LIB) $(HDRS)
 	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ tests/cpp/trace_rays.cpp -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'

@@ -381,6 +381,66 @@ int ort_trace_rays(ort_ctx* ctx, const ort_ray_query* q, void* stream);
  * copies not), from HIP events on its stream.  Only valid once that stream has passed the query. */
 int ort_last_query_ms(ort_ctx* ctx, float* ms);
 
+/* ---- progressive frames: a frame's samples accumulated over several calls --------------------
+ * The loop of an interactive caller (the reference's, src/main.cpp:120-163, with a camera driven
+ * by input): a cheap pass while the camera moves, a picture that keeps refining while it rests, a
+ * preview long before a many-sample frame is finished, a long frame cut into bounded submissions.
+ * An accumulation is an opaque object owned by its context.  It holds, per path slot of its tile,
+ * the pixel's RNG state and colour sum (20 bytes): a pixel is one sequential chain through its
+ * RNG state (glsl:640) and its samples are summed in order, so a frame accumulated in any number
+ * of passes ends bit-identical to ort_render_ex's frame of the same params, tile and output.
+ *   target   params->num_samples is the target N, fixed at ort_accum_begin: a sample's stratum is
+ *            s % (int)sqrt(N), s / (int)sqrt(N) (glsl:647-652), so sample s exists only relative to N.
+ *   begin    allocates the state and traces nothing.
+ *   pass     ort_accum_render traces the next min(n_samples, N - done) samples of every pixel of
+ *            the tile, each chain continued from its stored state, and stores the new state.
+ *   preview  with a non-NULL output the pass writes the picture of the k samples done so far:
+ *            pow(sum_k / k, 1/2.2) -- the divisor is the samples done, not N.  Any ort_output that
+ *            ort_render_ex takes (both formats, pitch, tile or frame placement; padding rows as
+ *            ort_render_ex writes them).  NULL output: accumulate without a picture.  With k == N
+ *            the picture is ort_render_ex's frame bit for bit, whatever the split into passes; a
+ *            preview at k < N with (int)sqrt(k) == (int)sqrt(N) is bit-identical to ort_render_ex
+ *            with num_samples = k (the same chain, strata and divisor); any other preview is the
+ *            first k samples of the N-sample chain, which no frame of k samples equals.
+ *   finished when done == N before the call nothing is traced, and a non-NULL output receives the
+ *            finished frame again, from the stored sums.
+ *   stream   as ort_render.  The passes of one accumulation are ordered by the caller: one stream,
+ *            or a wait between them.
+ *   isolation an accumulation keeps its own state, work counters and timing events, and neither
+ *            reads nor writes the context's per-frame render state (counter sets, speculation
+ *            buffers, heavy-first lists, frame timing): frames, ray queries and other accumulations
+ *            between two passes change nothing, in either direction.  Several may be alive on one
+ *            context.
+ *   options  ORT_OPT_KID_SKIP, ORT_OPT_EXACT_TRAVERSAL and ORT_OPT_PIXEL_LDS_SCENE apply per pass
+ *            (same pixels under every value).  Passes always take the whole-pixel kernel, whatever
+ *            ORT_OPT_PIXEL_PATHS says; they visit the tile's blocks in tile order.
+ *   scene    ort_upload_scene* / ort_build_scene invalidate the context's accumulations:
+ *            ort_accum_render then returns ORT_ERR_NO_SCENE ("the scene changed ..."), and
+ *            ort_accum_restart makes the accumulation usable again where the new scene allows it.
+ * ORT_ERR_INVALID_ARG, before anything is launched and with the state untouched: NULL arguments,
+ * n_samples < 1, params or a tile that ort_render refuses (num_samples < 1 included), an output
+ * that ort_render_ex refuses, an accumulation of another context, ort_accum_restart with another
+ * width, height, num_samples, max_depth or use_octree.  ORT_ERR_UNSUPPORTED at begin (and at a
+ * restart on a new scene): use_octree = 1 on the explicit layout, max_depth < 1 -- the
+ * whole-pixel kernel exists for the compact layout and brute force.  ORT_ERR_NO_SCENE: no scene.
+ * Not in scope: passes through the per-bounce pipeline (faster on the largest trees),
+ * speculation inside passes (ORT_OPT_PIXEL_SPECULATE), accumulations on an ort_group. */
+typedef struct ort_accum ort_accum;
+typedef struct ort_accum_info {
+    int32_t samples_done, samples_total;
+    int64_t device_bytes;     /* device memory the accumulation holds (state, counters, host-output staging) */
+} ort_accum_info;
+int ort_accum_begin(ort_ctx* ctx, const ort_params* params, const ort_tile* tile, ort_accum** out);
+int ort_accum_render(ort_ctx* ctx, ort_accum* accum, int32_t n_samples, const ort_output* output, void* stream);
+/* A new camera (view, position, zoom) for the same shape: samples_done back to 0, nothing allocated. */
+int ort_accum_restart(ort_ctx* ctx, ort_accum* accum, const ort_params* params);
+int ort_accum_get_info(const ort_accum* accum, ort_accum_info* info);
+/* Duration in milliseconds of the last pass's kernels (HIP events on its stream; the copy to a
+ * host output not included).  Only valid once that stream has passed the pass. */
+int ort_accum_last_pass_ms(ort_ctx* ctx, ort_accum* accum, float* ms);
+/* Frees the accumulation (NULL: ORT_OK); ort_destroy frees what is left. */
+int ort_accum_free(ort_ctx* ctx, ort_accum* accum);
+
 /* ---- several GPUs, one process --------------------------------------
  * The reference renders on one GL context; a caller of Raytracer::render() reaches the 8-GPU
  * configs through a group: one context per listed device (scene replicated), the frame cut

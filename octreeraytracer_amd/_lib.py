@@ -65,6 +65,8 @@ EXPORTED_SYMBOLS = (
     "ort_group_wait", "ort_group_set_timeout",
     "ort_render_ex", "ort_group_submit_fmt", "ort_group_render_fmt",
     "ort_trace_rays", "ort_last_query_ms",
+    "ort_accum_begin", "ort_accum_render", "ort_accum_restart", "ort_accum_get_info", "ort_accum_last_pass_ms",
+    "ort_accum_free",
 )
 ORT_GROUP_TRANSPORT_RCCL = 0
 ORT_GROUP_TRANSPORT_COPY = 1
@@ -124,6 +126,10 @@ class OrtSceneInfo(C.Structure):
     ]
 
 
+class OrtAccumInfo(C.Structure):
+    _fields_ = [("samples_done", C.c_int32), ("samples_total", C.c_int32), ("device_bytes", C.c_int64)]
+
+
 class OrtError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"ort error {code}: {msg}")
@@ -159,6 +165,12 @@ def _declare(lib, debug: str = "none"):
         "ort_render_ex": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(OrtOutput), _vp]),
         "ort_trace_rays": (C.c_int, [_vp, C.POINTER(OrtRayQuery), _vp]),
         "ort_last_query_ms": (C.c_int, [_vp, _fp]),
+        "ort_accum_begin": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(_vp)]),
+        "ort_accum_render": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(OrtOutput), _vp]),
+        "ort_accum_restart": (C.c_int, [_vp, _vp, C.POINTER(OrtParams)]),
+        "ort_accum_get_info": (C.c_int, [_vp, C.POINTER(OrtAccumInfo)]),
+        "ort_accum_last_pass_ms": (C.c_int, [_vp, _vp, _fp]),
+        "ort_accum_free": (C.c_int, [_vp, _vp]),
         "ort_last_kernel_ms": (C.c_int, [_vp, _fp]),
         "ort_last_trace_ms": (C.c_int, [_vp, _fp]),
         "ort_trace_times_ms": (C.c_int, [_vp, C.c_int, _fp]),
@@ -206,6 +218,9 @@ def _declare(lib, debug: str = "none"):
         "ort_debug_emulate_render": (C.c_int, [_fp, _fp, _fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip,
                                                C.c_int64, C.c_int32, C.POINTER(OrtParams), C.POINTER(OrtTile),
                                                _fp, _u64p]),
+        "ort_debug_emulate_render_prefix": (C.c_int, [_fp, _fp, _fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip,
+                                                      C.c_int64, C.c_int32, C.POINTER(OrtParams), C.POINTER(OrtTile),
+                                                      C.c_int32, _fp, _u64p]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("ort_debug_") and (debug == "none" or (debug == "present" and not hasattr(lib, name))):

@@ -22,6 +22,17 @@ int ort_debug_emulate_render(const float* sphere_center_radius, const float* sph
                              const int32_t* objects_offset, const int32_t* object_count, int32_t n_nodes,
                              const int32_t* object_indices, int64_t n_indices, int32_t layout,
                              const ort_params* params, const ort_tile* tile, float* rgb_out, uint64_t* counts);
+// TEST-ONLY: the picture an accumulation shows after samples_done of params->num_samples samples
+// (ort_accum_render's preview, stated on the CPU): the first samples_done samples of each pixel's
+// num_samples-sample chain -- in num_samples' strata -- divided by samples_done.  samples_done
+// 1 .. num_samples; -1 = all of them (ort_debug_emulate_render).
+int ort_debug_emulate_render_prefix(const float* sphere_center_radius, const float* sphere_mat_albedo,
+                                    const float* sphere_fuzz_ri, int32_t n_spheres, const float* node_min,
+                                    const float* node_max, const int32_t* children_offset,
+                                    const int32_t* objects_offset, const int32_t* object_count, int32_t n_nodes,
+                                    const int32_t* object_indices, int64_t n_indices, int32_t layout,
+                                    const ort_params* params, const ort_tile* tile, int32_t samples_done,
+                                    float* rgb_out, uint64_t* counts);
 // TEST-ONLY: the ort_group partition and assembly with an in-memory transport: each of the
 // `world` band tiles rendered by ort_debug_emulate_render, then assembled by the device
 // kernel's row map (group_map.h).  Full frame into rgb_out (host).

@@ -135,6 +135,9 @@ struct PipeArgs {
     // states; one with fx_slot runs the fixup list: pixel fx_slot[i] from sample fx_s0[i] with
     // state fx_st[i] and the colour sum of its earlier samples fx_col (three planes of total
     // floats), *fx_n entries
+    // An accumulation pass (ort_accum_render, PM 3: accum.inc) borrows four of these fields, indexed
+    // by path slot: samples `sample` .. sp_chunk - 1 of every pixel, from the RNG state fx_st[k] and
+    // the colour sum fx_col (three planes of total floats) when sample > 0, both stored back
     const float2* sp_prev;
     float2* sp_cur;
     float* sp_col;
@@ -1528,7 +1531,9 @@ __device__ __forceinline__ void block_account(const PipeArgs& A, int slot, int b
 // chain's order: the frames stay bit-identical, and a frame is no longer as long as its longest
 // pixel's chain (16 samples x 8 bounces at config.h's default).
 // PM: 0 whole pixels, 1 SPEC samples, 2 whole pixels that record their samples' end states or
-// run the fixup list (kept apart from 0: its registers are the ones-sample frames' too)
+// run the fixup list (kept apart from 0: its registers are the ones-sample frames' too), 3 a pass
+// of an accumulation (accum.inc: samples A.sample .. A.sp_chunk - 1 of every pixel, the chains'
+// states and sums kept per slot between passes; instantiated there, after every kernel of this file)
 template <int MODE, bool DEEP, bool LDS, int PM = 0>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_PIXEL_WAVES)))
 ort_pixel_paths(PipeArgs A) {
@@ -1669,6 +1674,17 @@ ort_pixel_paths(PipeArgs A) {
                                     st.x = v.x;
                                     st.y = v.y;
                                     col = ort::mk(A.fx_col[e], A.fx_col[(size_t)A.total + e], A.fx_col[2 * (size_t)A.total + e]);
+                                } else if (PM == 3) {  // the pass's first sample, from the slot's stored state and sum
+                                    s = A.sample;
+                                    if (s == 0) {
+                                        ort::pixel_rng_init(A.pp, px, py, st);
+                                        col = ort::mk(0.0f, 0.0f, 0.0f);
+                                    } else {
+                                        const float2 v = A.fx_st[k];
+                                        st.x = v.x;
+                                        st.y = v.y;
+                                        col = ort::mk(A.fx_col[k], A.fx_col[(size_t)A.total + k], A.fx_col[2 * (size_t)A.total + k]);
+                                    }
                                 } else {
                                     ort::pixel_rng_init(A.pp, px, py, st);
                                     s = 0;
@@ -1676,6 +1692,8 @@ ort_pixel_paths(PipeArgs A) {
                                 }
                                 ray = ort::primary_ray(A.pp, px, py, s, st);
                                 pixel = true;
+                            } else if (PM == 3) {  // ... of an accumulation pass: with a picture only
+                                if (A.out) store_padding(reread_args(A), cy, cx);
                             } else if (!SPEC) {  // a band's padding row (past the frame): zeros, as the pipeline writes
                                 store_padding(reread_args(A), cy, cx);
                             }
@@ -1727,11 +1745,23 @@ ort_pixel_paths(PipeArgs A) {
                 col = ort::add(col, c);
                 if (PM == 2 && A.sp_cur && ((s + 1) % A.sp_chunk == 0 || s + 1 == ns))  // a chunk's end state, for SPEC
                     A.sp_cur[(size_t)(s / A.sp_chunk) * A.total + k] = make_float2(st.x, st.y);
-                if (++s < ns) {
+                if (++s < (PM == 3 ? A.sp_chunk : ns)) {
                     b = 0;
                     c = ort::mk(1.0f, 1.0f, 1.0f);
                     importance = 1.0f;
                     ray = ort::primary_ray(A.pp, px, py, s, st);
+                } else if (PM == 3) {  // the pass's last sample: the slot's state and sum, and the picture of s samples
+                    A.fx_st[k] = make_float2(st.x, st.y);
+                    A.fx_col[k] = col.x;
+                    A.fx_col[(size_t)A.total + k] = col.y;
+                    A.fx_col[2 * (size_t)A.total + k] = col.z;
+                    const PipeArgs R = reread_args(A);
+                    if (R.out) {
+                        int cx, cy;
+                        (void)slot_coords(A, k, cx, cy);
+                        store_pixel(R, cy, cx, py, ort::finish_pixel(col, s));
+                    }
+                    k = -1;
                 } else {
                     int cx, cy;
                     (void)slot_coords(A, k, cx, cy);
@@ -2016,6 +2046,30 @@ struct ort_ctx {
     DevBuf q_keys, q_keys2, q_vals, q_list, q_temp;
     hipEvent_t qev0 = nullptr, qev1 = nullptr;
     bool q_timed = false;
+    // accumulations (ort_accum_*, accum.inc): the live ones, each with its own state, counters and
+    // events (ort_destroy frees what is left), and the scene's generation: free_scene advances
+    // it, and an accumulation begun or restarted under another one is stale
+    std::vector<ort_accum*> accums;
+    unsigned long long scene_gen = 0;
+};
+
+// A frame's samples accumulated over several passes (include/ort.h): the frame and tile it was
+// begun with, the samples done, and per path slot (tile-block order, as PipeArgs::total) the RNG
+// state (float2) followed by the colour sum's three planes -- 20 bytes a slot, each array read and
+// written by consecutive lanes for consecutive slots.
+struct ort_accum {
+    ort_ctx* ctx = nullptr;
+    ort_params p{};
+    ort_tile t{};
+    int mode = 0;          // 0 the compact layout's walk, 2 brute force
+    int done = 0;
+    long long blocks = 0;  // 16x16 tiles
+    unsigned long long scene_gen = 0;
+    DevBuf state;          // float2[slots] | float[3][slots]
+    DevBuf sync;           // the launch's cursor and done count (16 ints, zeroed before every pass)
+    DevBuf stage;          // host output: the tight picture on the device (allocated by the first such pass)
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;
 };
 
 namespace {
@@ -2056,6 +2110,17 @@ void free_scene(ort_ctx* c) {
     each_scene_buffer(*c, [](DevBuf& b) { free_buf(b); });
     ort::freeGpuTree(c->tree);
     c->has_scene = false;
+    c->scene_gen += 1;  // the accumulations begun on this scene are stale (accum.inc)
+}
+
+// An accumulation's device memory and events, and the object (its context's list is the caller's).
+void free_accum(ort_accum* a) {
+    free_buf(a->state);
+    free_buf(a->sync);
+    free_buf(a->stage);
+    if (a->ev0) (void)hipEventDestroy(a->ev0);
+    if (a->ev1) (void)hipEventDestroy(a->ev1);
+    delete a;
 }
 
 int upload(ort_ctx* ctx, DevBuf& b, const void* src, size_t bytes) {
@@ -2591,6 +2656,24 @@ int begin_counter_sets(ort_ctx* ctx, hipStream_t s, bool& fresh) {
     return ORT_OK;
 }
 
+// The dynamic LDS of an ort_pixel_paths launch on ctx's scene, and whether the scene itself lives
+// there (lds_scene; then a's lds_* fields say where).
+size_t pixel_paths_lds(const ort_ctx* ctx, int mode, PipeArgs& a, bool& lds_scene) {
+    size_t lds = mode == 0 ? lds_bytes(0, ctx->depth, true) : 0;
+    // an LDS-resident scene: node records + kid entries (16 B per node) and the leaf spheres
+    // (16 B per entry: objectIndices, then the per-sphere tail), when they fit the budget
+    const size_t nk_b = 16 * (size_t)ctx->n_nodes, sph_b = 16 * ((size_t)ctx->n_indices + (size_t)ctx->n_spheres);
+    lds_scene = mode == 0 && ctx->depth <= 8 && a.S.nk && ctx->pixel_lds_scene && nk_b + sph_b <= (size_t)kPixelLdsSceneBytes;
+    if (lds_scene) {
+        a.lds_nk_off = (int)align16(lds);
+        a.lds_sph_off = (int)(a.lds_nk_off + nk_b);
+        a.lds_nk_n16 = (int)(nk_b / 16);
+        a.lds_sph_n16 = (int)(sph_b / 16);
+        lds = (size_t)a.lds_sph_off + sph_b;
+    }
+    return lds;
+}
+
 // The frame as one ort_pixel_paths launch (use_pixel_paths); dout: the frame on the device.
 int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int mode, const DevOutput& dout,
                        hipStream_t s) {
@@ -2684,19 +2767,8 @@ int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int
         ctx->pp_sig = sig;
     }
     const bool deep = ctx->depth > 8;
-    size_t lds = mode == 0 ? lds_bytes(0, ctx->depth, true) : 0;
-    // an LDS-resident scene: node records + kid entries (16 B per node) and the leaf spheres
-    // (16 B per entry: objectIndices, then the per-sphere tail), when they fit the budget
-    const size_t nk_b = 16 * (size_t)ctx->n_nodes, sph_b = 16 * ((size_t)ctx->n_indices + (size_t)ctx->n_spheres);
-    const bool lds_scene = mode == 0 && !deep && a.S.nk && ctx->pixel_lds_scene &&
-                           nk_b + sph_b <= (size_t)kPixelLdsSceneBytes;
-    if (lds_scene) {
-        a.lds_nk_off = (int)align16(lds);
-        a.lds_sph_off = (int)(a.lds_nk_off + nk_b);
-        a.lds_nk_n16 = (int)(nk_b / 16);
-        a.lds_sph_n16 = (int)(sph_b / 16);
-        lds = (size_t)a.lds_sph_off + sph_b;
-    }
+    bool lds_scene;
+    const size_t lds = pixel_paths_lds(ctx, mode, a, lds_scene);
     const int fslot = (int)(ctx->frames % ort_ctx::kRing);
     ctx->tseg[fslot] = 0;
     const int nseg = spec_frame ? 3 : 1;  // SPEC: the samples, the resolve, the fixup list
@@ -3336,6 +3408,8 @@ int ort_destroy(ort_ctx* ctx) {
     if (!ctx) return ORT_OK;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    for (ort_accum* a : ctx->accums) free_accum(a);
+    ctx->accums.clear();
     free_scene(ctx);
     free_buf(ctx->scratch_out);
     free_buf(ctx->counters);
@@ -3744,9 +3818,21 @@ int ort_debug_emulate_render(const float* cr, const float* ma, const float* fr, 
                              const float* node_min, const float* node_max, const int32_t* co, const int32_t* oo,
                              const int32_t* cnt, int32_t n_nodes, const int32_t* idx, int64_t n_indices,
                              int32_t layout, const ort_params* p, const ort_tile* t, float* out, uint64_t* counts) {
+    return ort_debug_emulate_render_prefix(cr, ma, fr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices,
+                                           layout, p, t, -1, out, counts);
+}
+
+int ort_debug_emulate_render_prefix(const float* cr, const float* ma, const float* fr, int32_t n_spheres,
+                                    const float* node_min, const float* node_max, const int32_t* co, const int32_t* oo,
+                                    const int32_t* cnt, int32_t n_nodes, const int32_t* idx, int64_t n_indices,
+                                    int32_t layout, const ort_params* p, const ort_tile* t, int32_t samples_done,
+                                    float* out, uint64_t* counts) {
     try {
         const std::string bad = check_frame_tile(p, t);
         if (!bad.empty()) return fail(nullptr, ORT_ERR_INVALID_ARG, bad);
+        if (samples_done >= 0 && (samples_done < 1 || samples_done > p->num_samples))
+            return fail(nullptr, ORT_ERR_INVALID_ARG, "samples_done must be 1 .. num_samples");
+        const int done = samples_done < 0 ? -1 : samples_done;
         ort::SceneInput in{cr, ma, fr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices};
         const std::string vbad = ort::validateScene(in);
         if (!vbad.empty()) return fail(nullptr, ORT_ERR_INVALID_ARG, vbad);
@@ -3827,15 +3913,15 @@ int ort_debug_emulate_render(const float* cr, const float* ma, const float* fr, 
                 // pixels must agree bit for bit
                 if (mode == 0) {
                     v = ort::shade_pixel<0, false>(pp, S, fplanes.data(), fplanes_b.data(), rank_lut, lf, nullptr, nullptr,
-                                                   t->x0 + c, y, cc);
+                                                   t->x0 + c, y, cc, done);
                     vc = ort::shade_pixel<0, true>(pp, S, fplanes.data(), fplanes_b.data(), rank_lut, lf, nullptr, nullptr,
-                                                   t->x0 + c, y, cc);
+                                                   t->x0 + c, y, cc, done);
                 } else if (mode == 1) {
-                    v = ort::shade_pixel<1, false>(pp, S, nullptr, nullptr, nullptr, lf, snode.data(), stmin.data(), t->x0 + c, y, cc);
-                    vc = ort::shade_pixel<1, true>(pp, S, nullptr, nullptr, nullptr, lf, snode.data(), stmin.data(), t->x0 + c, y, cc);
+                    v = ort::shade_pixel<1, false>(pp, S, nullptr, nullptr, nullptr, lf, snode.data(), stmin.data(), t->x0 + c, y, cc, done);
+                    vc = ort::shade_pixel<1, true>(pp, S, nullptr, nullptr, nullptr, lf, snode.data(), stmin.data(), t->x0 + c, y, cc, done);
                 } else {
-                    v = ort::shade_pixel<2, false>(pp, S, nullptr, nullptr, nullptr, lf, nullptr, nullptr, t->x0 + c, y, cc);
-                    vc = ort::shade_pixel<2, true>(pp, S, nullptr, nullptr, nullptr, lf, nullptr, nullptr, t->x0 + c, y, cc);
+                    v = ort::shade_pixel<2, false>(pp, S, nullptr, nullptr, nullptr, lf, nullptr, nullptr, t->x0 + c, y, cc, done);
+                    vc = ort::shade_pixel<2, true>(pp, S, nullptr, nullptr, nullptr, lf, nullptr, nullptr, t->x0 + c, y, cc, done);
                 }
                 if (ort::f2u(v.x) != ort::f2u(vc.x) || ort::f2u(v.y) != ort::f2u(vc.y) || ort::f2u(v.z) != ort::f2u(vc.z))
                     return fail(nullptr, ORT_ERR_INTERNAL, "emulation: production and counting walks differ at pixel (" +
@@ -4206,3 +4292,6 @@ int ort_debug_pop_coverage(uint64_t* hb_pops, uint64_t* sign_masks, int32_t rese
 // Ray queries (ort_trace_rays, ort_last_query_ms, ort_debug_query_rays): after the render path, so
 // that its kernels keep their places in the code object.
 #include "ray_query.inc"
+// Progressive frames (ort_accum_*): last, so that the passes' ort_pixel_paths<..., 3> instances and
+// the resolve kernel follow every other kernel.
+#include "accum.inc"

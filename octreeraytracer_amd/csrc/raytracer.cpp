@@ -3,6 +3,7 @@
 
 #include <chrono>
 #include <cmath>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -105,6 +106,7 @@ void Raytracer::setupBuffers() {
 void Raytracer::cleanupBuffers() {
     if (dframe) (void)hipFree(dframe);
     dframe = nullptr;
+    accum = nullptr;  // (ort_destroy frees it)
     if (ctx) ort_destroy(ctx);
     if (group) ort_group_destroy(group);
     ctx = nullptr;
@@ -156,6 +158,33 @@ int Raytracer::traceRays(const ort_ray* rays, int64_t n, ort_ray_hit* hits, floa
     }
     const ort_ray_query q = {rays, n, hits, normals, 0, cfg.useOctree, 0, 0};
     return ort_trace_rays(ctx, &q, nullptr);
+}
+
+int Raytracer::renderProgressive(const Camera& cam, int samples, float* rgb, int* samplesDone) {
+    if (!ctx && !group && !initialize()) return ORT_ERR_HIP;
+    if (group) return ORT_ERR_UNSUPPORTED;  // accumulations live on one context
+    if (!sceneReady) {
+        setupScene();
+        setupBuffers();
+        if (!sceneReady) return ORT_ERR_INVALID_ARG;
+    }
+    const ort_params p = frameParams(cam);
+    int rc = ORT_OK;
+    if (!accum) {
+        const ort_tile t{0, width, 0, height, 0, 0};
+        if ((rc = ort_accum_begin(ctx, &p, &t, &accum)) != ORT_OK) return rc;
+        accumParams = p;
+    } else if (std::memcmp(p.view, accumParams.view, sizeof p.view) != 0 ||
+               std::memcmp(p.camera_position, accumParams.camera_position, sizeof p.camera_position) != 0 ||
+               p.camera_zoom != accumParams.camera_zoom) {  // the camera moved: the frame starts again
+        if ((rc = ort_accum_restart(ctx, accum, &p)) != ORT_OK) return rc;
+        accumParams = p;
+    }
+    const ort_output o = {rgb, 0, ORT_FORMAT_RGB32F, ORT_PLACE_TILE, 0, 0};
+    rc = ort_accum_render(ctx, accum, samples, &o, nullptr);
+    ort_accum_info info{};
+    if (samplesDone && ort_accum_get_info(accum, &info) == ORT_OK) *samplesDone = info.samples_done;
+    return rc;
 }
 
 int Raytracer::render(const Camera& cam, float* rgb) {

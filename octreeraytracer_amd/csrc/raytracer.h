@@ -88,6 +88,14 @@ public:
     // Host pointers; builds and uploads the scene on first use, like render.  Single-device
     // configurations only (a group: ORT_ERR_UNSUPPORTED).
     int traceRays(const ort_ray* rays, int64_t n, ort_ray_hit* hits, float* normals = nullptr);
+    // The interactive loop's frame (include/ort.h ort_accum_*): `samples` more of the frame's
+    // cfg.numSamples samples per pixel, then the picture of the samples done so far into rgb (as
+    // render(cam, rgb); divided by the samples done, so every call's picture is a frame).  It
+    // continues the current accumulation while cam's view, position and zoom are the ones it was
+    // begun with, and starts again otherwise; with all samples done the picture is render()'s, bit
+    // for bit, and further calls write it again.  samplesDone (may be nullptr) receives the samples
+    // in the picture.  Single-device configurations only (a group: ORT_ERR_UNSUPPORTED).
+    int renderProgressive(const Camera& cam, int samples, float* rgb, int* samplesDone = nullptr);
 
     Camera camera;  // the reference keeps a global Camera (src/main.cpp:18); pose set like main()
     const RaytracerConfig& config() const { return cfg; }
@@ -126,6 +134,8 @@ private:
     std::vector<float> frame;
     float* dframe = nullptr;       // run()'s device frame (readback off), on the context's device
     int renderRun();               // one frame of run(): into dframe, or into `frame` with readback
+    ort_accum* accum = nullptr;    // renderProgressive's accumulation (the context owns it) and its camera
+    ort_params accumParams{};
     double gpuBuildSeconds = 0.0;
     StatsWork work;               // counted after the timed frames when cfg.extendedStats
 

@@ -1925,13 +1925,18 @@ ORT_FN uint32_t pack_rgba8(V3 v) {
 // main() of the fragment shader (glsl:636-664) for pixel (px, py), py = 0 the bottom row,
 // as one sequential chain of the steps above (host emulation).
 // planes_b: the bounce walk's plane tables (trace_ray).
+// done: the samples taken, P.ns by default; fewer is the picture an accumulation shows after
+// `done` samples (ort_accum_render): the first `done` samples of the P.ns-sample chain, in P.ns's
+// strata, divided by `done`.
 template <int MODE, bool COUNT, class Frames>
 ORT_FN V3 shade_pixel(const PixelParams& P, const KScene& S, const float* planes, const float* planes_b,
-                      const uint8_t* rank_lut, Frames& fr, int* snode, float* stmin, int px, int py, Counters& cnt) {
+                      const uint8_t* rank_lut, Frames& fr, int* snode, float* stmin, int px, int py, Counters& cnt,
+                      int done = -1) {
+    if (done < 0) done = P.ns;
     ort_rng st;
     pixel_rng_init(P, px, py, st);
     V3 col = mk(0.0f, 0.0f, 0.0f);
-    for (int s = 0; s < P.ns; ++s) {
+    for (int s = 0; s < done; ++s) {
         Ray ray = primary_ray(P, px, py, s, st);
         V3 c = mk(1.0f, 1.0f, 1.0f);
         float importance = 1.0f;
@@ -1943,13 +1948,13 @@ ORT_FN V3 shade_pixel(const PixelParams& P, const KScene& S, const float* planes
             HitRec h;
             if (tr == ORT_TRACE_HIT) h = hit_record<MODE>(S, ray, t, entry);
             const bool hit = tr == ORT_TRACE_HIT;
-            const bool fin = b == P.maxDepth - 1 && s == P.ns - 1;  // the RNG state is dead after it
+            const bool fin = b == P.maxDepth - 1 && s == done - 1;  // the RNG state is dead after it
             if (fin ? shade_bounce<true>(hit, h, ray, c, importance, st) : shade_bounce(hit, h, ray, c, importance, st))
                 break;
         }
         col = add(col, c);
     }
-    return finish_pixel(col, P.ns);
+    return finish_pixel(col, done);
 }
 
 // --- ray queries (ort_trace_rays): a caller's ray -> {t, sphere, normal} ---

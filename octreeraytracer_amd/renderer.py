@@ -284,10 +284,18 @@ class Renderer:
         tile = tile or Tile.full(params)
         p, t = params.to_c(), tile.to_c()
         s = C.c_void_p(int(stream)) if stream else None
+        o, out = self._output("render", params, tile, out, format, row_pitch, place)
+        self._check(self._lib.ort_render_ex(self._ctx, C.byref(p), C.byref(t), C.byref(o), s))
+        return out
+
+    def _output(self, what, params, tile, out, format, row_pitch, place):
+        """The ort_output of a call `what` (render, Accumulation.step) that writes the tile into out
+        -- None (a new numpy array), a numpy array, a device pointer or a torch CUDA tensor -- and
+        the object the call returns: the buffer checked against the bytes the description covers."""
         if format not in L.FORMATS:
-            raise ValueError(f"render: format must be one of {sorted(L.FORMATS)} (got {format!r})")
+            raise ValueError(f"{what}: format must be one of {sorted(L.FORMATS)} (got {format!r})")
         if place not in L.PLACEMENTS:
-            raise ValueError(f"render: place must be one of {sorted(L.PLACEMENTS)} (got {place!r})")
+            raise ValueError(f"{what}: place must be one of {sorted(L.PLACEMENTS)} (got {place!r})")
         fmt, plc = L.FORMATS[format], L.PLACEMENTS[place]
         bpp = L.FORMAT_BPP[fmt]
         np_dtype, channels = (np.float32, 3) if fmt == L.ORT_FORMAT_RGB32F else (np.uint8, 4)
@@ -296,37 +304,41 @@ class Renderer:
         n_rows = params.height if plc == L.ORT_PLACE_FRAME else tile.rows
         pitch = row_bytes if row_pitch is None else int(row_pitch)
         if pitch % 4 != 0:
-            raise ValueError(f"render: row_pitch must be a multiple of 4 (got {pitch})")
+            raise ValueError(f"{what}: row_pitch must be a multiple of 4 (got {pitch})")
         if pitch < row_bytes:
-            raise ValueError(f"render: row_pitch {pitch} is below the row's {row_bytes} bytes")
+            raise ValueError(f"{what}: row_pitch {pitch} is below the row's {row_bytes} bytes")
         need = (n_rows - 1) * pitch + row_bytes if n_rows > 0 else 0
         if out is None:
             if plc == L.ORT_PLACE_FRAME or row_pitch is not None:
-                raise ValueError("render: place='frame' and row_pitch describe a caller's buffer: pass out")
+                raise ValueError(f"{what}: place='frame' and row_pitch describe a caller's buffer: pass out")
             out = np.empty((tile.rows, tile.width, channels), np_dtype)
         o = L.OrtOutput(None, 0, fmt, plc, 0, 0 if row_pitch is None else pitch)
         if isinstance(out, np.ndarray):
             if plc == L.ORT_PLACE_FRAME:
-                raise ValueError("render: place='frame' writes device memory: out must be a device pointer or tensor")
+                raise ValueError(f"{what}: place='frame' writes device memory: out must be a device pointer or tensor")
             if out.dtype != np_dtype or not out.flags.c_contiguous or out.nbytes < need:
-                raise ValueError(f"render: out must be a C-contiguous {np.dtype(np_dtype).name} array of >= {need} "
+                raise ValueError(f"{what}: out must be a C-contiguous {np.dtype(np_dtype).name} array of >= {need} "
                                  f"bytes (got {out.dtype}, {out.nbytes} bytes, contiguous={out.flags.c_contiguous})")
             o.data = out.ctypes.data_as(C.c_void_p)
-            self._check(self._lib.ort_render_ex(self._ctx, C.byref(p), C.byref(t), C.byref(o), s))
-            return out
+            return o, out
         ptr = out.data_ptr() if hasattr(out, "data_ptr") else int(out)
         if hasattr(out, "numel"):  # a torch tensor: the format's dtype, contiguous, on this context's GPU
             import torch
             t_dtype = torch.float32 if fmt == L.ORT_FORMAT_RGB32F else torch.uint8
             nbytes = out.numel() * out.element_size()
             if out.dtype != t_dtype or not out.is_contiguous() or nbytes < need:
-                raise ValueError(f"render: out must be a contiguous {t_dtype} tensor of >= {need} bytes "
+                raise ValueError(f"{what}: out must be a contiguous {t_dtype} tensor of >= {need} bytes "
                                  f"(got {out.dtype}, {nbytes} bytes, contiguous={out.is_contiguous()})")
             if out.device.type != "cuda" or out.device.index != self.device:
-                raise ValueError(f"render: out is on {out.device}, the context renders on cuda:{self.device}")
+                raise ValueError(f"{what}: out is on {out.device}, the context renders on cuda:{self.device}")
         o.data, o.is_device = C.c_void_p(ptr), 1
-        self._check(self._lib.ort_render_ex(self._ctx, C.byref(p), C.byref(t), C.byref(o), s))
-        return out
+        return o, out
+
+    # -- progressive frames -----------------------------------------------------------
+    def accumulate(self, params: FrameParams, tile: Tile | None = None) -> "Accumulation":
+        """Begin accumulating the frame `params` (its num_samples is the target N) over several
+        calls: ort_accum_begin (include/ort.h).  Allocates the per-pixel state, traces nothing."""
+        return Accumulation(self, params, tile or Tile.full(params))
 
     # -- ray queries ------------------------------------------------------------------
     def trace_rays(self, rays, *, use_octree=True, sort=False, normals=False, out=None, stream=None, n=None):
@@ -454,6 +466,86 @@ class Renderer:
         return dict(zip(L.COUNT_NAMES, [int(v) for v in counts]))
 
 
+class Accumulation:
+    """A frame's samples accumulated over several calls (``Renderer.accumulate``; ort_accum_* in
+    include/ort.h).  ``step(n)`` traces the next n samples of every pixel and returns the picture
+    of the samples done so far -- divided by the samples done, so every step's picture is a
+    frame; with all of them done it is ``Renderer.render``'s frame bit for bit, whatever the steps.
+    A context manager: leaving it frees the state (as ``close`` does; the renderer's ``close``
+    frees what is left)."""
+
+    def __init__(self, renderer: Renderer, params: FrameParams, tile: Tile):
+        self._r = renderer
+        self._h = C.c_void_p()
+        self.params, self.tile = params, tile
+        p, t = params.to_c(), tile.to_c()
+        renderer._check(renderer._lib.ort_accum_begin(renderer._ctx, C.byref(p), C.byref(t), C.byref(self._h)))
+
+    def close(self):
+        if self._h and self._r._ctx:
+            self._r._check(self._r._lib.ort_accum_free(self._r._ctx, self._h))
+        self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        i = L.OrtAccumInfo()
+        self._r._check(self._r._lib.ort_accum_get_info(self._h, C.byref(i)))
+        return {"samples_done": i.samples_done, "samples_total": i.samples_total, "device_bytes": i.device_bytes}
+
+    @property
+    def done(self) -> int:
+        return self.info()["samples_done"]
+
+    @property
+    def total(self) -> int:
+        return self.info()["samples_total"]
+
+    @property
+    def finished(self) -> bool:
+        i = self.info()
+        return i["samples_done"] >= i["samples_total"]
+
+    def step(self, n: int = 1, out=None, stream=None, *, format: str = "rgb32f", row_pitch: int | None = None,
+             place: str = "tile"):
+        """Trace the next min(n, total - done) samples of every pixel and write the picture of the
+        samples done so far; on a finished accumulation, write the finished frame again.  out,
+        stream, format, row_pitch, place: as ``Renderer.render``, which this returns like;
+        out=False accumulates without a picture and returns None."""
+        r = self._r
+        s = C.c_void_p(int(stream)) if stream else None
+        if out is False:
+            r._check(r._lib.ort_accum_render(r._ctx, self._h, int(n), None, s))
+            return None
+        o, out = r._output("step", self.params, self.tile, out, format, row_pitch, place)
+        r._check(r._lib.ort_accum_render(r._ctx, self._h, int(n), C.byref(o), s))
+        return out
+
+    def restart(self, params: FrameParams):
+        """A new camera for the same shape (width, height, num_samples, max_depth, use_octree):
+        samples done back to 0, nothing allocated.  Also what makes the accumulation usable again
+        after the renderer's scene changed."""
+        p = params.to_c()
+        self._r._check(self._r._lib.ort_accum_restart(self._r._ctx, self._h, C.byref(p)))
+        self.params = params
+
+    def last_pass_ms(self) -> float:
+        """The last step's kernels, from HIP events on its stream."""
+        ms = C.c_float()
+        self._r._check(self._r._lib.ort_accum_last_pass_ms(self._r._ctx, self._h, C.byref(ms)))
+        return ms.value
+
+
 # Reference-layout record bytes touched, SURVEY.md 8(d): the algorithmic traffic model.
 BYTES_PER = {"nodes_popped": 36, "child_records": 32, "leaf_objects": 20, "accepted_hits": 32, "pixels": 12}
 
@@ -463,10 +555,12 @@ def algorithmic_bytes(counts: dict) -> int:
 
 
 def emulate_render_host(spheres: SphereSet, tree: FlatOctree | None, params: FrameParams, tile: Tile | None = None,
-                        layout: int = L.ORT_LAYOUT_COMPACT):
+                        layout: int = L.ORT_LAYOUT_COMPACT, samples_done: int | None = None):
     """TEST-ONLY: run the kernel's per-pixel code (render_core.h) on the host CPU.
     Used by the CPU test suite to validate the kernel's traversal logic against the
-    independent oracle without a GPU.  ``Renderer.render`` never calls this."""
+    independent oracle without a GPU.  ``Renderer.render`` never calls this.
+    samples_done = k: the picture an ``Accumulation`` of params shows after k samples -- the
+    first k samples of each pixel's num_samples-sample chain, divided by k."""
     lib = L.analysis_lib()
     tile = tile or Tile.full(params)
     out = np.empty((tile.rows, tile.width, 3), np.float32)
@@ -484,8 +578,12 @@ def emulate_render_host(spheres: SphereSet, tree: FlatOctree | None, params: Fra
             (tree.objects_offset, np.int32), (tree.object_count, np.int32), (tree.object_indices, np.int32)))
         args = (L.fptr(keep[0]), L.fptr(keep[1]), L.iptr(keep[2]), L.iptr(keep[3]), L.iptr(keep[4]),
                 tree.n_nodes, L.iptr(keep[5]), tree.n_indices)
-    L.acheck(lib.ort_debug_emulate_render(L.fptr(cr), L.fptr(ma), L.fptr(fr), spheres.n, *args, layout,
-                                         C.byref(p), C.byref(t), L.fptr(out), counts))
+    if samples_done is None:
+        L.acheck(lib.ort_debug_emulate_render(L.fptr(cr), L.fptr(ma), L.fptr(fr), spheres.n, *args, layout,
+                                             C.byref(p), C.byref(t), L.fptr(out), counts))
+    else:
+        L.acheck(lib.ort_debug_emulate_render_prefix(L.fptr(cr), L.fptr(ma), L.fptr(fr), spheres.n, *args, layout,
+                                                    C.byref(p), C.byref(t), int(samples_done), L.fptr(out), counts))
     del keep
     return out, dict(zip(L.COUNT_NAMES, [int(v) for v in counts]))
 
