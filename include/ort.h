@@ -69,7 +69,11 @@ typedef struct ort_params {
  * (band_height <= 0 means one band: y = y0 + j).  Pixel rows are GL rows: y = 0 is the
  * BOTTOM row of the image.  Columns are x0 .. x0+width-1.  Rows with y >= height are
  * written as zeros.  The RNG seed and the camera always use the full-frame resolution,
- * so any tiling produces the same pixels as a full-frame render. */
+ * so any tiling produces the same pixels as a full-frame render.
+ * A tile of no pixels (width == 0 or rows == 0) is valid: ort_render, ort_render_ex and
+ * ort_count_traffic return ORT_OK without launching anything, the output is left untouched
+ * (a NULL data pointer is accepted for it; every counter is zero), and the context's per-frame
+ * state is as it was. */
 typedef struct ort_tile {
     int32_t x0, width;
     int32_t y0, rows;
@@ -404,6 +408,9 @@ int ort_last_query_ms(ort_ctx* ctx, float* ms);
  *            first k samples of the N-sample chain, which no frame of k samples equals.
  *   finished when done == N before the call nothing is traced, and a non-NULL output receives the
  *            finished frame again, from the stored sums.
+ *   no pixels an accumulation of a tile of no pixels (ort_tile) is valid: a pass launches nothing,
+ *            leaves its output untouched (NULL data is accepted) and still counts its samples as
+ *            done, so the accumulation finishes after N of them like any other.
  *   stream   as ort_render.  The passes of one accumulation are ordered by the caller: one stream,
  *            or a wait between them.
  *   isolation an accumulation keeps its own state, work counters and timing events, and neither

@@ -3647,6 +3647,13 @@ int ort_count_traffic(ort_ctx* ctx, const ort_params* params, const ort_tile* ti
     if (pix) HIPCHK(ctx, hipMalloc(&tmp.p, 12 * pix));
     const ort_output o = {tmp.p, 1, ORT_FORMAT_RGB32F, ORT_PLACE_TILE, 0, 0};
     const int rc = render_impl(ctx, params, tile, &o, nullptr, (unsigned long long*)ctx->counters.p);
+    if (rc == ORT_OK && !pix) {
+        // a tile of no pixels: render_impl launched nothing and waited for nothing, so the memset
+        // above may still be queued on the context's (non-blocking) stream, which the copy below
+        // does not wait for -- it would return the counters of the count before this one
+        for (int k = 0; k < ORT_COUNT_N; ++k) counts[k] = 0;
+        return ORT_OK;
+    }
     if (rc == ORT_OK) {
         unsigned long long h[8] = {0};
         hipError_t e = hipMemcpy(h, ctx->counters.p, 64, hipMemcpyDeviceToHost);
