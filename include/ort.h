@@ -364,8 +364,8 @@ int ort_count_traffic(ort_ctx* ctx, const ort_params* params, const ort_tile* ti
  * n_rays == 0: ORT_OK, nothing launched.  ORT_ERR_INVALID_ARG, before anything is launched: NULL
  * q, n_rays < 0 or > 2^30, NULL rays or hits with n_rays > 0, unknown flag bits, reserved != 0,
  * pointers that are not 4-byte aligned.  ORT_ERR_NO_SCENE: no scene, or use_octree = 1 on a
- * scene uploaded without a tree.  Not in scope: a caller-chosen (t_min, t_max), camera-ray
- * generation, queries on an ort_group. */
+ * scene uploaded without a tree.  Not in scope: a caller-chosen (t_min, t_max), queries on an
+ * ort_group.  (A frame's camera rays: ort_trace_camera below.) */
 typedef struct ort_ray     { float origin[3]; float direction[3]; } ort_ray;   /* 24 bytes */
 typedef struct ort_ray_hit { float t; int32_t sphere; } ort_ray_hit;           /* 8 bytes */
 #define ORT_QUERY_SORT 1
@@ -384,6 +384,55 @@ int ort_trace_rays(ort_ctx* ctx, const ort_ray_query* q, void* stream);
 /* Duration in milliseconds of the last ort_trace_rays' kernels (the sort's included, the host
  * copies not), from HIP events on its stream.  Only valid once that stream has passed the query. */
 int ort_last_query_ms(ort_ctx* ctx, float* ms);
+
+/* ---- camera queries: each pixel's camera ray and what it hits (picking under the cursor, id /
+ * depth / normal images, guide buffers beside a progressive preview) -----------------------------
+ * ort_trace_camera makes, for every pixel of a tile, the camera ray the shader makes for it and
+ * walks it as ort_trace_rays walks a caller's ray: the caller restates neither the camera
+ * (Camera_initFromViewMatrix, glsl:176-202) nor the pixel's RNG draws, and no ray crosses the bus.
+ *   which   ORT_CAMERA_FIRST_SAMPLE: the ray radiance() receives for sample 0 of the pixel --
+ *           the RNG seeded with FragCoord / iResolution (glsl:640), the two stratum draws of
+ *           stratum (0, 0) of (int)sqrt(params->num_samples) (glsl:647-652), Camera_getRay's two
+ *           jitter draws and its lens disk (glsl:205-221), radiance()'s normalize (glsl:602).  With
+ *           num_samples = 1 the record is the first intersectScene of the pixel's only path.
+ *           ORT_CAMERA_PIXEL_CENTRE: the pinhole ray through the pixel centre -- Camera_getRay at
+ *           s = (x + 0.5) / width, t = (y + 0.5) / height with the jitter and the lens offset left
+ *           out (origin = the camera's position), normalised twice as the shader does; no RNG
+ *           draw, independent of num_samples.
+ *   records one per tile pixel: index = output row j x tile->width + column, j -> pixel row y as
+ *           ort_render maps it (ort_tile: bands, GL rows, y = 0 at the bottom).  Rows with
+ *           y >= height get the miss record {0.0f, -1}, a zero normal and a zero ray.  The RNG
+ *           seed and the camera always use the full frame's size: any tiling of a frame gives the
+ *           full frame's records.
+ *   rays    NULL, or the ray of every tile pixel as it was walked.
+ *   hits    NULL, or intersectScene(ray, 0.001, MAXFLOAT) by params->use_octree on the resident
+ *           layout: bit-identical to ort_trace_rays over the rays this call writes.  NULL with
+ *           rays set is ray generation only: nothing is walked and no scene is needed.
+ *   normals NULL, or 3 floats per tile pixel as ort_trace_rays writes them; needs hits.
+ * params->max_depth is not read.  on_device, stream, the staging of host pointers and
+ * ort_last_query_ms: as ort_trace_rays, whose buffers and events this call shares (order the
+ * queries of one context on one stream, or let one finish before the next starts on another); it
+ * reads and writes no per-frame render or accumulation state.  ORT_OPT_KID_SKIP,
+ * ORT_OPT_EXACT_TRAVERSAL and ORT_OPT_REFILL apply as they do to ort_trace_rays (same records).
+ * A tile of no pixels: ORT_OK, nothing launched.  ORT_ERR_INVALID_ARG, before anything is launched
+ * and with the outputs untouched: a params or tile ort_render refuses (num_samples < 1 among
+ * them), NULL q, unknown which, reserved != 0, rays and hits both NULL, normals without hits,
+ * pointers that are not 4-byte aligned, a tile of more than 2^30 pixels.  ORT_ERR_NO_SCENE (with
+ * hits): no scene, or use_octree = 1 on a scene uploaded without a tree.  Not in scope: samples
+ * other than 0 (their RNG state depends on the earlier paths), queries on an ort_group, a
+ * caller-chosen (t_min, t_max). */
+#define ORT_CAMERA_FIRST_SAMPLE 0  /* the ray radiance() receives for sample 0 of the pixel */
+#define ORT_CAMERA_PIXEL_CENTRE 1  /* pinhole ray through the pixel centre: no RNG draw, no lens offset */
+typedef struct ort_camera_query {
+    ort_ray*     rays;      /* NULL, or one record per tile pixel: the ray that was walked */
+    ort_ray_hit* hits;      /* NULL, or one record per tile pixel */
+    float*       normals;   /* NULL, or 3 floats per tile pixel (needs hits) */
+    int32_t on_device;      /* != 0: all three are device pointers on ctx's device */
+    int32_t which;          /* ORT_CAMERA_* */
+    int32_t reserved[2];    /* 0 */
+} ort_camera_query;
+int ort_trace_camera(ort_ctx* ctx, const ort_params* params, const ort_tile* tile,
+                     const ort_camera_query* q, void* stream);
 
 /* ---- progressive frames: a frame's samples accumulated over several calls --------------------
  * The loop of an interactive caller (the reference's, src/main.cpp:120-163, with a camera driven

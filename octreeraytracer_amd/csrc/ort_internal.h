@@ -74,6 +74,15 @@ int ort_debug_query_rays(const float* sphere_center_radius, int32_t n_spheres, c
                          const int32_t* object_count, int32_t n_nodes, const int32_t* object_indices, int64_t n_indices,
                          int32_t layout, int32_t use_octree, const float* rays, int64_t n_rays, ort_ray_hit* hits,
                          float* normals);
+// TEST-ONLY: ort_trace_camera on the host CPU: the kernels' per-pixel ray (camera_query.inc
+// camera_query_ray) for every pixel of the tile, then ort_debug_query_rays over those rays by
+// params->use_octree.  rays (6 floats), hits, normals (3 floats) per tile pixel, each may be NULL
+// as in ort_camera_query; with hits NULL no scene array is read.
+int ort_debug_camera_query(const float* sphere_center_radius, int32_t n_spheres, const float* node_min,
+                           const float* node_max, const int32_t* children_offset, const int32_t* objects_offset,
+                           const int32_t* object_count, int32_t n_nodes, const int32_t* object_indices, int64_t n_indices,
+                           int32_t layout, const ort_params* params, const ort_tile* tile, int32_t which, float* rays,
+                           ort_ray_hit* hits, float* normals);
 // ANALYSIS-ONLY: lane overlap of sampled 8x8 primary-ray blocks (tools/wave_stats.py).
 int ort_debug_wave_stats(const float* sphere_center_radius, const float* sphere_mat_albedo,
                          const float* sphere_fuzz_ri, int32_t n_spheres, const float* node_min,

@@ -4302,3 +4302,6 @@ int ort_debug_pop_coverage(uint64_t* hb_pops, uint64_t* sign_masks, int32_t rese
 // Progressive frames (ort_accum_*): last, so that the passes' ort_pixel_paths<..., 3> instances and
 // the resolve kernel follow every other kernel.
 #include "accum.inc"
+// Camera queries (ort_trace_camera, ort_debug_camera_query): after ray_query.inc, whose walk and
+// buffers they share, and after accum.inc, so that every earlier kernel keeps its place.
+#include "camera_query.inc"

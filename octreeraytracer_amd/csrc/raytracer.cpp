@@ -160,6 +160,31 @@ int Raytracer::traceRays(const ort_ray* rays, int64_t n, ort_ray_hit* hits, floa
     return ort_trace_rays(ctx, &q, nullptr);
 }
 
+int Raytracer::traceCamera(const Camera& cam, const ort_tile& tile, const ort_camera_query& query) {
+    if (!ctx && !group && !initialize()) return ORT_ERR_HIP;
+    if (group) return ORT_ERR_UNSUPPORTED;  // queries run on one context
+    if (!sceneReady) {
+        setupScene();
+        setupBuffers();
+        if (!sceneReady) return ORT_ERR_INVALID_ARG;
+    }
+    const ort_params p = frameParams(cam);
+    return ort_trace_camera(ctx, &p, &tile, &query, nullptr);
+}
+
+int Raytracer::pick(const Camera& cam, int x, int y, ort_ray_hit* hit, float point[3]) {
+    ort_ray ray;
+    ort_ray_hit h = {0.0f, -1};
+    const ort_tile tile{x, 1, y, 1, 0, 0};
+    const ort_camera_query q = {&ray, &h, nullptr, 0, ORT_CAMERA_PIXEL_CENTRE, {0, 0}};
+    const int rc = traceCamera(cam, tile, q);
+    if (rc != ORT_OK) return rc;
+    if (hit) *hit = h;
+    if (point)
+        for (int k = 0; k < 3; ++k) point[k] = ray.origin[k] + h.t * ray.direction[k];
+    return ORT_OK;
+}
+
 int Raytracer::renderProgressive(const Camera& cam, int samples, float* rgb, int* samplesDone) {
     if (!ctx && !group && !initialize()) return ORT_ERR_HIP;
     if (group) return ORT_ERR_UNSUPPORTED;  // accumulations live on one context

@@ -88,6 +88,17 @@ public:
     // Host pointers; builds and uploads the scene on first use, like render.  Single-device
     // configurations only (a group: ORT_ERR_UNSUPPORTED).
     int traceRays(const ort_ray* rays, int64_t n, ort_ray_hit* hits, float* normals = nullptr);
+    // Camera queries (include/ort.h ort_trace_camera): for every pixel of the tile of cam's frame
+    // (cfg's size, samples and walk) the camera ray the frame is drawn with and what it hits --
+    // query.rays, .hits, .normals and .which as ort_camera_query describes them.  Synchronous;
+    // builds and uploads the scene on first use.  Single-device configurations only (a group:
+    // ORT_ERR_UNSUPPORTED).
+    int traceCamera(const Camera& cam, const ort_tile& tile, const ort_camera_query& query);
+    // The sphere under pixel (x, y) of cam's frame, by the pinhole ray through the pixel centre
+    // (ORT_CAMERA_PIXEL_CENTRE): *hit = {t, sphere index in getSpheres()} ({0, -1}: nothing
+    // there), point (may be nullptr) = origin + t * direction.  y is a GL row, 0 at the bottom:
+    // for a cursor at window row wy (0 at the top) pass height - 1 - wy.
+    int pick(const Camera& cam, int x, int y, ort_ray_hit* hit, float point[3] = nullptr);
     // The interactive loop's frame (include/ort.h ort_accum_*): `samples` more of the frame's
     // cfg.numSamples samples per pixel, then the picture of the samples done so far into rgb (as
     // render(cam, rgb); divided by the samples done, so every call's picture is a frame).  It

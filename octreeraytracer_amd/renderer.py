@@ -424,8 +424,114 @@ class Renderer:
         self._check(self._lib.ort_trace_rays(self._ctx, C.byref(q), s))
         return (out, normals) if want_normals else out
 
+    # -- camera queries ---------------------------------------------------------------
+    def trace_camera(self, params: FrameParams, tile: Tile | None = None, *, which: str = "first_sample", rays=False,
+                     normals=False, out=None, stream=None, hits: bool = True):
+        """Each tile pixel's camera ray and what it hits (ort_trace_camera, include/ort.h): the ray
+        the shader makes for the pixel, walked as ``trace_rays`` walks a caller's ray.
+
+        which: "first_sample" -- the ray of sample 0 of params.num_samples, RNG draws, jitter and
+        lens offset included: with num_samples = 1 the first intersection of the pixel's only
+        path -- or "pixel_centre", the pinhole ray through the pixel centre (no RNG, the same for
+        every num_samples).  Records are in the tile's output order (row j as ``Tile.pixel_rows``
+        maps it, GL rows); rows past the frame hold a miss, a zero normal and a zero ray.
+
+        Host (out None or a numpy array, rays and normals True / False): returns t float32 and
+        sphere int32, each (rows, width) -- (0.0, -1) for a miss -- then, where asked, normals
+        (rows, width, 3) and rays (rows, width, 6: origin, direction).  out may be a C-contiguous
+        int32 array of at least 2 * rows * width elements to receive the records {t bits, sphere}.
+        Device (any of out, rays, normals a torch CUDA tensor on this device or a device pointer):
+        everything stays on the device; out receives {t bits, sphere} int32 records, rays 6 and
+        normals 3 float32 per pixel; rays=True / normals=True / out=None allocate tensors shaped
+        (rows, width, 2 | 6 | 3).  Returns out, then normals, then rays, those that were asked for
+        (one object when it is the only one).
+        hits=False with rays: ray generation only -- nothing is walked, no scene is needed;
+        returns the rays.  stream: as render()."""
+        tile = tile or Tile.full(params)
+        if which not in L.CAMERA_RAYS:
+            raise ValueError(f"trace_camera: which must be one of {sorted(L.CAMERA_RAYS)} (got {which!r})")
+        rows, width = int(tile.rows), int(tile.width)
+        if rows < 0 or width < 0:
+            raise ValueError("trace_camera: negative tile size")
+        n = rows * width
+        is_flag = lambda x: isinstance(x, (bool, np.bool_))  # noqa: E731
+        want_rays = not is_flag(rays) or bool(rays)
+        want_normals = not is_flag(normals) or bool(normals)
+        if not hits and (not want_rays or want_normals or out is not None):
+            raise ValueError("trace_camera: hits=False is ray generation only: rays, and neither normals nor out")
+        p, t = params.to_c(), tile.to_c()
+        s = C.c_void_p(int(stream)) if stream else None
+        q = L.OrtCameraQuery(None, None, None, 0, L.CAMERA_RAYS[which])
+        device = any(x is not None and not is_flag(x) and not isinstance(x, np.ndarray) for x in (out, rays, normals))
+        if not device:
+            if not is_flag(rays) or not is_flag(normals):
+                raise ValueError("trace_camera: with host output, rays and normals are True or False")
+            if hits:
+                if out is None:
+                    out = np.empty((n, 2), np.int32)
+                if out.dtype != np.int32 or not out.flags.c_contiguous or out.nbytes < 8 * n:
+                    raise ValueError(f"trace_camera: out must be a C-contiguous int32 numpy array of >= {8 * n} bytes")
+                q.hits = out.ctypes.data_as(C.c_void_p)
+            nrm = np.zeros((rows, width, 3), np.float32) if want_normals else None
+            ray = np.zeros((rows, width, 6), np.float32) if want_rays else None
+            q.normals = nrm.ctypes.data_as(C.c_void_p) if want_normals else None
+            q.rays = ray.ctypes.data_as(C.c_void_p) if want_rays else None
+            self._check(self._lib.ort_trace_camera(self._ctx, C.byref(p), C.byref(t), C.byref(q), s))
+            if not hits:
+                return ray
+            rec = out.reshape(-1)[:2 * n].reshape(n, 2)
+            res = (np.ascontiguousarray(rec[:, 0]).view(np.float32).reshape(rows, width),
+                   np.ascontiguousarray(rec[:, 1]).reshape(rows, width))
+            return res + ((nrm,) if want_normals else ()) + ((ray,) if want_rays else ())
+
+        def device_arg(x, what, dtype_name, need):  # a torch CUDA tensor on this device, or a pointer
+            if hasattr(x, "data_ptr"):
+                nbytes = x.numel() * x.element_size()
+                if str(x.dtype) != "torch." + dtype_name or not x.is_contiguous() or nbytes < need:
+                    raise ValueError(f"trace_camera: {what} must be a contiguous {dtype_name} tensor of >= {need} bytes "
+                                     f"(got {x.dtype}, {nbytes} bytes, contiguous={x.is_contiguous()})")
+                if x.device.type != "cuda" or x.device.index != self.device:
+                    raise ValueError(f"trace_camera: {what} is on {x.device}, the context traces on cuda:{self.device}")
+                return x.data_ptr()
+            if not isinstance(x, (int, np.integer)):
+                raise ValueError(f"trace_camera: {what} must be a torch CUDA tensor or a device pointer (int)")
+            return int(x)
+
+        def allocate(last, dtype_name):
+            import torch
+            return torch.empty((rows, width, last), dtype=getattr(torch, dtype_name), device=torch.device("cuda", self.device))
+
+        if hits and out is None:
+            out = allocate(2, "int32")
+        if is_flag(rays) and rays:
+            rays = allocate(6, "float32")
+        if is_flag(normals) and normals:
+            normals = allocate(3, "float32")
+        if hits:
+            q.hits = C.c_void_p(device_arg(out, "out", "int32", 8 * n))
+        if want_normals:
+            q.normals = C.c_void_p(device_arg(normals, "normals", "float32", 12 * n))
+        if want_rays:
+            q.rays = C.c_void_p(device_arg(rays, "rays", "float32", 24 * n))
+        q.on_device = 1
+        self._check(self._lib.ort_trace_camera(self._ctx, C.byref(p), C.byref(t), C.byref(q), s))
+        res = ((out,) if hits else ()) + ((normals,) if want_normals else ()) + ((rays,) if want_rays else ())
+        return res[0] if len(res) == 1 else res
+
+    def pick(self, params: FrameParams, x: int, y: int, *, which: str = "pixel_centre"):
+        """The sphere under pixel (x, y): (sphere, t, point) from a one-pixel camera query --
+        sphere the index in the uploaded arrays (-1: nothing there, t = 0.0 and point = the ray's
+        origin), point = origin + t * direction in float32, shape (3,).  y is a GL row (0 at the bottom):
+        for a cursor at window row wy, top row 0, pass y = params.height - 1 - wy.  which: as
+        ``trace_camera``; the default is the ray through the pixel centre, "first_sample" with
+        num_samples = 1 picks what a one-sample frame drew at the pixel."""
+        t, sphere, ray = self.trace_camera(params, Tile(int(x), 1, int(y), 1), which=which, rays=True)
+        o, d = ray[0, 0, :3], ray[0, 0, 3:]
+        point = (o + (t[0, 0] * d).astype(np.float32)).astype(np.float32)
+        return int(sphere[0, 0]), float(t[0, 0]), point
+
     def last_query_ms(self) -> float:
-        """The last trace_rays' kernels (its sort included), from HIP events on its stream."""
+        """The last trace_rays' or trace_camera's kernels (a sort included), from HIP events on its stream."""
         ms = C.c_float()
         self._check(self._lib.ort_last_query_ms(self._ctx, C.byref(ms)))
         return ms.value
@@ -612,3 +718,38 @@ def query_rays_host(spheres: SphereSet, tree: FlatOctree | None, rays, *, layout
     del keep
     t, sph = np.ascontiguousarray(rec[:, 0]).view(np.float32), np.ascontiguousarray(rec[:, 1])
     return (t, sph, nrm) if normals else (t, sph)
+
+
+def camera_query_host(spheres: SphereSet | None, tree: FlatOctree | None, params: FrameParams, tile: Tile | None = None,
+                      *, which: str = "first_sample", layout: int = L.ORT_LAYOUT_COMPACT, hits: bool = True,
+                      normals: bool = False):
+    """TEST-ONLY: ``Renderer.trace_camera`` on the host CPU (ort_debug_camera_query: the kernels' own
+    per-pixel ray, then render_core.h query_ray by params.use_octree).  Returns (rays (rows, width,
+    6), t, sphere (rows, width)[, normals (rows, width, 3)]); with hits=False the rays alone, and
+    spheres may be None."""
+    lib = L.analysis_lib()
+    tile = tile or Tile.full(params)
+    rows, width = int(tile.rows), int(tile.width)
+    p, t = params.to_c(), tile.to_c()
+    rays = np.zeros((rows, width, 6), np.float32)
+    rec = np.zeros((rows * width, 2), np.int32) if hits else None
+    nrm = np.zeros((rows, width, 3), np.float32) if normals else None
+    cr = np.ascontiguousarray(spheres.center_radius, np.float32) if spheres is not None else None
+    if tree is None or not hits:
+        keep = ()
+        args = (None, None, None, None, None, 0, None, 0)
+    else:
+        keep = tuple(np.ascontiguousarray(a, t_) for a, t_ in (
+            (tree.node_min, np.float32), (tree.node_max, np.float32), (tree.children_offset, np.int32),
+            (tree.objects_offset, np.int32), (tree.object_count, np.int32), (tree.object_indices, np.int32)))
+        args = (L.fptr(keep[0]), L.fptr(keep[1]), L.iptr(keep[2]), L.iptr(keep[3]), L.iptr(keep[4]),
+                tree.n_nodes, L.iptr(keep[5]), tree.n_indices)
+    L.acheck(lib.ort_debug_camera_query(L.fptr(cr), spheres.n if spheres is not None else 0, *args, int(layout),
+                                       C.byref(p), C.byref(t), L.CAMERA_RAYS[which], L.fptr(rays),
+                                       rec.ctypes.data_as(C.c_void_p) if hits else None, L.fptr(nrm)))
+    del keep
+    if not hits:
+        return rays
+    tt = np.ascontiguousarray(rec[:, 0]).view(np.float32).reshape(rows, width)
+    sph = np.ascontiguousarray(rec[:, 1]).reshape(rows, width)
+    return (rays, tt, sph, nrm) if normals else (rays, tt, sph)

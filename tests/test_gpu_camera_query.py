@@ -1,0 +1,377 @@
+"""Camera queries on the GPU (ort_trace_camera, include/ort.h): the kernels' rays equal the host
+emulation's bit for bit (which tests/test_camera_query.py pins to the oracle), their records equal
+ort_trace_rays over those rays, the emulation's and the oracle's intersectScene, on every walk:
+the persistent fast walk with its deferred exact walk (compact layout, depth 5 and 10), the
+explicit layout's stack walk and brute force.  Every comparison is exact."""
+import ctypes as C
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import camera_sets as cs
+import ray_sets
+from camera_sets import bits
+from octreeraytracer_amd import _lib as L
+from octreeraytracer_amd.renderer import camera_query_host
+from test_camera_query import oracle_records
+from test_gpu_ray_query import make_renderer
+from test_ray_query import CONFIGS
+
+pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parents[1]
+FILL = 0x5A5A5A5A
+
+
+@pytest.fixture(scope="module")
+def renderers(ort):
+    made = {}
+
+    def get(name):
+        if name not in made:
+            made[name] = make_renderer(ort, name)
+        return made[name]
+
+    yield get
+    for r in made.values():
+        r.close()
+
+
+@pytest.fixture(scope="module")
+def full(renderers):
+    """(name, w, h, ns, which) -> (t, sphere, normals, rays) of the whole frame by the plain host
+    call (read-only)."""
+    done = {}
+
+    def get(name, w=37, h=21, ns=1, which="first_sample"):
+        key = (name, w, h, ns, which)
+        if key not in done:
+            res = renderers(name).trace_camera(cs.params(name, w, h, ns), which=which, rays=True, normals=True)
+            for a in res:
+                a.flags.writeable = False
+            done[key] = res
+        return done[key]
+
+    return get
+
+
+def same(got, want):
+    return len(got) == len(want) and all(g.shape == w.shape and np.array_equal(bits(g), bits(w)) for g, w in zip(got, want))
+
+
+def emulated(name, w=37, h=21, ns=1, which="first_sample"):
+    rays, tt, sph, nrm = cs.emulated(name, w, h, ns, which)
+    return tt, sph, nrm, rays  # in trace_camera's order
+
+
+@pytest.mark.parametrize("which", cs.WHICH)
+@pytest.mark.parametrize("w,h,ns", [(37, 21, 1), (64, 8, 4), (37, 21, 5), (64, 8, 1)])
+@pytest.mark.parametrize("name", cs.SCENES)
+def test_records_equal_the_emulation_trace_rays_and_the_oracle(ort, oracle, renderers, full, name, w, h, ns, which):
+    got = full(name, w, h, ns, which)
+    tt, sph, nrm, rays = got
+    assert tt.shape == (h, w) and sph.shape == (h, w) and nrm.shape == (h, w, 3) and rays.shape == (h, w, 6)
+    assert same(got, emulated(name, w, h, ns, which))
+    flat = np.ascontiguousarray(rays.reshape(-1, 6))
+    q = renderers(name).trace_rays(flat, use_octree=CONFIGS[name][1], normals=True)
+    assert same((tt.reshape(-1), sph.reshape(-1), nrm.reshape(-1, 3)), q)
+    ref = oracle_records(ort, oracle, name, rays)
+    hit = sph.reshape(-1) >= 0
+    assert np.array_equal(hit, ref[:, 0] == 1) and np.array_equal(bits(tt).reshape(-1)[hit], ref[hit, 1])
+    if (w, h) == (37, 21):
+        assert 0.2 <= hit.mean() <= 0.8
+    if (w, h, ns, which) == (37, 21, 1, "first_sample"):
+        s, _, _ = ray_sets.scene(name)
+        ray_sets.check_spheres_against_the_oracle(ort, oracle, s, flat, bits(tt).reshape(-1), sph.reshape(-1))
+        assert np.array_equal(bits(nrm.reshape(-1, 3)), bits(ray_sets.numpy_normals(s, flat, tt.reshape(-1), sph.reshape(-1))))
+
+
+@pytest.mark.parametrize("which", cs.WHICH)
+@pytest.mark.parametrize("name", cs.SCENES)
+def test_any_tiling_gives_the_frames_records(ort, renderers, full, name, which):
+    """Left / right at an odd column, a banded tile (band_height 3, band_stride 7), a tile
+    reaching 2 rows past the frame ({0, -1}, zero normals and rays there)."""
+    r, p = renderers(name), cs.params(name, ns=4)
+    want = full(name, ns=4, which=which)
+
+    def q(tile):
+        return r.trace_camera(p, tile, which=which, rays=True, normals=True)
+
+    left, right = q(ort.Tile(0, 13, 0, 21)), q(ort.Tile(13, 24, 0, 21))
+    assert same([np.concatenate([a, b], axis=1) for a, b in zip(left, right)], want)
+    band = ort.Tile(5, 20, 1, 9, 3, 7)
+    ys = band.pixel_rows(21)
+    assert same(q(band), [a[ys, 5:25] for a in want])
+    over = q(ort.Tile(0, 37, 17, 6))
+    assert same([a[:4] for a in over], [a[17:] for a in want])
+    tt, sph, nrm, rays = over
+    assert (bits(tt[4:]) == 0).all() and (sph[4:] == -1).all() and (bits(nrm[4:]) == 0).all() and (bits(rays[4:]) == 0).all()
+    # a band whose last rows fall below the frame's top row
+    band = ort.Tile(0, 37, 12, 6, 3, 7)
+    ys = band.pixel_rows(21)
+    assert list(ys) == [12, 13, 14, 19, 20, 21]
+    got = q(band)
+    assert same([a[:5] for a in got], [a[ys[:5]] for a in want])
+    assert (got[1][5] == -1).all() and (bits(got[0][5]) == 0).all() and (bits(got[3][5]) == 0).all()
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 129])
+@pytest.mark.parametrize("name", cs.SCENES)
+def test_pixel_counts_around_a_wave(ort, renderers, name, n):
+    """1-row tiles of 1, 63, 64, 65 and 129 pixels of a 129 x 5 frame: chunk and wave edges."""
+    s, t, _ = ray_sets.scene(name)
+    layout, use_octree = CONFIGS[name]
+    p = cs.params(name, 129, 5, 4)
+    tile = ort.Tile(0, n, 2, 1)
+    got = renderers(name).trace_camera(p, tile, rays=True, normals=True)
+    rays, tt, sph, nrm = camera_query_host(s, t if use_octree else None, p, tile, layout=layout, normals=True)
+    assert same(got, (tt, sph, nrm, rays))
+    assert got[0].shape == (1, n)
+
+
+@pytest.mark.parametrize("name", cs.SCENES)
+def test_output_combinations(ort, renderers, full, name):
+    """hits only; rays only; all three; into an oversized out whose tail keeps its fill."""
+    r, p = renderers(name), cs.params(name)
+    tt, sph, nrm, rays = full(name)
+    assert same(r.trace_camera(p), (tt, sph))
+    assert same(r.trace_camera(p, normals=True), (tt, sph, nrm))
+    assert same(r.trace_camera(p, rays=True), (tt, sph, rays))
+    only = r.trace_camera(p, rays=True, hits=False)
+    assert np.array_equal(bits(only), bits(rays))
+    out = np.full((37 * 21 + 3, 2), FILL, np.int32)
+    got = r.trace_camera(p, out=out, normals=True, rays=True)
+    assert same(got, (tt, sph, nrm, rays))
+    assert np.array_equal(out[:777, 0], bits(tt).reshape(-1)) and np.array_equal(out[:777, 1], sph.reshape(-1))
+    assert (out[777:] == FILL).all()
+    assert r.last_query_ms() > 0.0
+
+
+def test_rays_only_needs_no_scene(ort, full):
+    p = cs.params("compact5", ns=4)
+    with ort.Renderer(0) as r:
+        for which in cs.WHICH:
+            got = r.trace_camera(p, which=which, rays=True, hits=False)
+            assert np.array_equal(bits(got), bits(full("compact5", ns=4, which=which)[3]))
+        assert r.last_query_ms() > 0.0
+        with pytest.raises(ort.OrtError) as e:
+            r.trace_camera(p)
+        assert e.value.code == L.ORT_ERR_NO_SCENE
+
+
+@pytest.mark.parametrize("name", cs.SCENES)
+def test_device_outputs_and_streams(renderers, full, name):
+    """Torch tensors equal the host call; so does a stream-ordered call on a torch stream after a
+    synchronise, a raw-pointer call, and ray generation alone into a tensor."""
+    import torch
+    r, p = renderers(name), cs.params(name)
+    tt, sph, nrm, rays = full(name)
+    n = 37 * 21
+
+    def check(out, d_nrm, d_rays, what):
+        torch.cuda.synchronize()
+        if out is not None:
+            o = out.cpu().numpy().reshape(-1, 2)
+            assert np.array_equal(o[:n, 0], bits(tt).reshape(-1)) and np.array_equal(o[:n, 1], sph.reshape(-1)), what
+        if d_nrm is not None:
+            assert np.array_equal(bits(d_nrm.cpu().numpy()).reshape(-1)[:3 * n], bits(nrm).reshape(-1)), what
+        if d_rays is not None:
+            assert np.array_equal(bits(d_rays.cpu().numpy()).reshape(-1)[:6 * n], bits(rays).reshape(-1)), what
+
+    out = torch.full((n + 5, 2), -7, dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
+    got = r.trace_camera(p, out=out)
+    assert got is out
+    check(out, None, None, "hits into a tensor")
+    assert (out[n:].cpu().numpy() == -7).all()
+    out1, nrm1, rays1 = r.trace_camera(p, out=out, normals=True, rays=True)
+    assert out1 is out and nrm1.shape == (21, 37, 3) and rays1.shape == (21, 37, 6) and rays1.dtype == torch.float32
+    check(out1, nrm1, rays1, "allocated normals and rays")
+    only = torch.full((n, 6), -7.0, dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+    assert r.trace_camera(p, rays=only, hits=False) is only
+    check(None, None, only, "rays only")
+    st = torch.cuda.Stream(device="cuda:0")
+    out3 = torch.full((n, 2), -7, dtype=torch.int32, device="cuda:0")
+    nrm3 = torch.full((n, 3), -7.0, dtype=torch.float32, device="cuda:0")
+    rays3 = torch.full((n, 6), -7.0, dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+    got = r.trace_camera(p, out=out3, normals=nrm3, rays=rays3, stream=st.cuda_stream)
+    assert got[0] is out3 and got[1] is nrm3 and got[2] is rays3
+    st.synchronize()
+    check(out3, nrm3, rays3, "stream-ordered")
+    out4 = torch.full((n, 2), -7, dtype=torch.int32, device="cuda:0")
+    rays4 = torch.full((n, 6), -7.0, dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+    r.trace_camera(p, out=out4.data_ptr(), rays=rays4.data_ptr())
+    check(out4, None, rays4, "pointers")
+    assert r.last_query_ms() > 0.0
+
+
+@pytest.mark.parametrize("name", ["compact5", "compact10"])
+def test_options_leave_the_records_alone(ort, full, name):
+    """ORT_OPT_KID_SKIP 0 / 1 / 2, ORT_OPT_REFILL 1 / 16 / 64 and ORT_OPT_EXACT_TRAVERSAL: same records."""
+    s, t, _ = ray_sets.scene(name)
+    p = cs.params(name)
+    want = full(name)
+    with ort.Renderer(0) as r:
+        r.upload(s, t)
+        for skip in (0, 2, 1):
+            r.set_kid_skip(skip)
+            assert same(r.trace_camera(p, rays=True, normals=True), want), f"kid skip {skip}"
+        for refill in (1, 64, 16):
+            r.set_refill(refill)
+            assert same(r.trace_camera(p, rays=True, normals=True), want), f"refill {refill}"
+        r.set_exact_traversal(True)
+        assert same(r.trace_camera(p, rays=True, normals=True), want), "exact traversal"
+        assert same(r.trace_camera(p, which="pixel_centre", rays=True, normals=True), full(name, which="pixel_centre"))
+
+
+@pytest.mark.parametrize("ns,depth", [(1, 1), (2, 4)])
+def test_render_query_render(ort, scene_c1, ns, depth):
+    """A camera query between two frames changes neither: both equal the frame of a context that
+    never queried; and the query repeated gives the same records."""
+    s, t = scene_c1
+    p = ort.FrameParams.default_camera(37, 21, num_samples=ns, max_depth=depth, **cs.CAMERAS["explicit"])
+    with ort.Renderer(0) as r:
+        r.upload(s, t)
+        plain = r.render(p)
+        plain2 = r.render(p)
+    with ort.Renderer(0) as r:
+        r.upload(s, t)
+        a = r.render(p)
+        q1 = r.trace_camera(p, rays=True, normals=True)
+        q1c = r.trace_camera(p, which="pixel_centre", rays=True, normals=True)
+        b = r.render(p)
+        q2 = r.trace_camera(p, rays=True, normals=True)
+        c = r.render(p)
+        q2c = r.trace_camera(p, which="pixel_centre", rays=True, normals=True)
+    for f in (plain2, a, b, c):
+        assert np.array_equal(f.view(np.uint32), plain.view(np.uint32))
+    assert same(q1, q2) and same(q1c, q2c) and not same(q1, q1c)
+    assert 0.2 <= (q1[1] >= 0).mean() <= 0.8
+
+
+def test_a_query_between_the_passes_of_an_accumulation(ort, scene_c1):
+    s, t = scene_c1
+    p = ort.FrameParams.default_camera(37, 21, num_samples=4, max_depth=3, **cs.CAMERAS["explicit"])
+    with ort.Renderer(0) as r:
+        r.upload(s, t)
+        want = r.render(p)
+        with r.accumulate(p) as acc:
+            acc.step(1)
+            q1 = r.trace_camera(p, rays=True, normals=True)
+            acc.step(2)
+            q2 = r.trace_camera(p, rays=True, normals=True)
+            got = acc.step(1)
+            assert acc.finished
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+        assert same(q1, q2) and (q1[1] >= 0).any()
+
+
+@pytest.mark.parametrize("which", cs.WHICH)
+@pytest.mark.parametrize("name", ["compact5", "explicit"])
+def test_pick(renderers, full, name, which):
+    """pick at three pixels is the full query's record there, and point = o + t d in float32."""
+    r, p = renderers(name), cs.params(name)
+    tt, sph, _, rays = full(name, which=which)
+    ys, xs = np.nonzero(sph >= 0)
+    miss = np.argwhere(sph < 0)[0]
+    picks = [(int(xs[0]), int(ys[0])), (int(xs[-1]), int(ys[-1])), (int(miss[1]), int(miss[0]))]
+    for x, y in picks:
+        sphere, t, point = r.pick(p, x, y, which=which)
+        assert sphere == sph[y, x] and np.float32(t).view(np.int32) == bits(tt)[y, x]
+        o, d = rays[y, x, :3], rays[y, x, 3:]
+        want = (o + (tt[y, x] * d).astype(np.float32)).astype(np.float32)
+        assert point.dtype == np.float32 and np.array_equal(bits(point), bits(want))
+    assert r.pick(p, *picks[0])[0] == full(name, which="pixel_centre")[1][picks[0][1], picks[0][0]]  # the default
+
+
+def raw(r, p, tile, rays=None, hits=None, normals=None, which=0, reserved=(0, 0), null_q=False):
+    def ptr(a):
+        return a.ctypes.data_as(C.c_void_p) if a is not None else None
+    q = L.OrtCameraQuery(ptr(rays), ptr(hits), ptr(normals), 0, which, (C.c_int32 * 2)(*reserved))
+    pc, tc = p.to_c(), tile.to_c()
+    return r._lib.ort_trace_camera(r._ctx, C.byref(pc), C.byref(tc), None if null_q else C.byref(q), None)
+
+
+def test_error_codes(ort):
+    s, t, _ = ray_sets.scene("explicit")
+    p = cs.params("explicit", 8, 4)
+    tile = ort.Tile.full(p)
+    rays = np.full((32, 6), FILL, np.int32)
+    hits = np.full((32, 2), FILL, np.int32)
+    nrm = np.full((32, 3), FILL, np.int32)
+    bad = L.ORT_ERR_INVALID_ARG
+    with ort.Renderer(0) as r:
+        assert raw(r, p, tile, rays, hits) == L.ORT_ERR_NO_SCENE
+        r.upload(s, t)
+        assert raw(r, p, tile) == bad                                   # both NULL
+        assert raw(r, p, tile, rays, None, nrm) == bad                  # normals without hits
+        assert raw(r, p, tile, rays, hits, which=2) == bad
+        assert raw(r, p, tile, rays, hits, which=-1) == bad
+        assert raw(r, p, tile, rays, hits, reserved=(1, 0)) == bad
+        assert raw(r, p, tile, rays, hits, reserved=(0, 1)) == bad
+        assert raw(r, p, tile, rays, hits, null_q=True) == bad
+        assert raw(r, cs.params("explicit", 8, 4, ns=0), tile, rays, hits) == bad   # as ort_render refuses it
+        assert raw(r, cs.params("explicit", 8, 4, ns=0), tile, rays, hits, which=1) == bad
+        assert raw(r, p, ort.Tile(4, 8, 0, 4), rays, hits) == bad      # columns outside the frame
+        assert raw(r, p, ort.Tile(0, 8, -1, 4), rays, hits) == bad
+        assert raw(r, p, ort.Tile(0, 8, 0, 4, 3, 2), rays, hits) == bad  # band_stride < band_height
+        wide = cs.params("explicit", 1 << 16, 4)
+        assert raw(r, wide, ort.Tile(0, 1 << 16, 0, (1 << 14) + 1), rays, hits) == bad  # more than 2^30 pixels
+        for k in range(3):  # each pointer misaligned in turn
+            odd = np.zeros(32 * 24 + 4, np.uint8)[1:1 + 32 * 24]
+            assert odd.ctypes.data % 4 != 0
+            args = [rays, hits, nrm]
+            args[k] = odd
+            assert raw(r, p, tile, *args) == bad
+        with pytest.raises(ort.OrtError) as e:
+            r.render(cs.params("explicit", 8, 4, ns=0))
+        assert e.value.code == bad
+        for a in (rays, hits, nrm):
+            assert (a == FILL).all()  # refused before anything was launched
+        assert raw(r, p, ort.Tile(0, 8, 0, 0), rays, hits, nrm) == L.ORT_OK  # nothing to do
+        assert raw(r, p, ort.Tile(3, 0, 0, 4), rays, hits, nrm) == L.ORT_OK
+        for a in (rays, hits, nrm):
+            assert (a == FILL).all()
+        assert raw(r, p, tile, rays, hits, nrm) == L.ORT_OK
+        assert (hits != FILL).all() and (rays != FILL).all() and (nrm != FILL).all()
+        r.upload(s, None)  # no tree: the octree walk is refused as ort_render refuses it
+        assert raw(r, p, tile, rays, hits) == L.ORT_ERR_NO_SCENE
+        assert raw(r, p, tile, rays, None) == L.ORT_OK  # ray generation needs none
+        p0 = cs.params("brute", 8, 4)
+        assert raw(r, p0, tile, rays, hits) == L.ORT_OK
+
+
+@pytest.mark.parametrize("brute", [False, True])
+def test_cpp_pick_prints_the_python_records(ort, brute):
+    """build/pick (Raytracer::traceCamera and ::pick on the DEBUG scene) against Renderer.trace_camera
+    and Renderer.pick, on a tile of the DEBUG view that holds a sphere's edge."""
+    exe = ROOT / "build" / "pick"
+    assert exe.exists(), "make examples"
+    x0, y0, w, h = 7, 8, 11, 10
+    res = subprocess.run([str(exe)] + (["--brute"] if brute else []) + [str(v) for v in (x0, y0, w, h)],
+                         capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr
+    rows = [l.split()[1:] for l in res.stdout.splitlines() if l.startswith("rec ")]
+    picked = [l.split()[1:] for l in res.stdout.splitlines() if l.startswith("pick ")]
+    assert len(rows) == 2 * w * h and len(picked) == 1
+    s = ort.debug_spheres()
+    p = ort.FrameParams.default_camera(64, 48, use_octree=0 if brute else 1, position=(30.0, 20.0, -50.0))
+    with ort.Renderer(0) as r:
+        r.upload(s, ort.build_octree(s, 3, 2))  # RaytracerConfig's debugDepth, debugSpheresPerNode
+        for k, which in enumerate(cs.WHICH):
+            tt, sph, nrm, rays = r.trace_camera(p, ort.Tile(x0, w, y0, h), which=which, rays=True, normals=True)
+            assert 0.1 <= (sph >= 0).mean() <= 0.9
+            for i, row in enumerate(rows[k * w * h:(k + 1) * w * h]):
+                j, c = divmod(i, w)
+                assert [int(v) for v in row[:4]] == [k, i, int(sph[j, c] >= 0), sph[j, c]], (which, i, row)
+                want = np.concatenate([tt[j, c:c + 1], nrm[j, c], rays[j, c]]).view(np.uint32)
+                assert [int(v, 16) for v in row[4:]] == [int(v) for v in want], (which, i, row)
+        sphere, t, point = r.pick(p, x0, y0)
+        f = picked[0]
+        assert [int(f[0]), int(f[1]), int(f[2])] == [x0, y0, sphere]
+        assert [int(v, 16) for v in f[3:]] == [int(v) for v in np.concatenate([[np.float32(t)], point]).astype(np.float32).view(np.uint32)]
