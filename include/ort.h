@@ -364,8 +364,9 @@ int ort_count_traffic(ort_ctx* ctx, const ort_params* params, const ort_tile* ti
  * n_rays == 0: ORT_OK, nothing launched.  ORT_ERR_INVALID_ARG, before anything is launched: NULL
  * q, n_rays < 0 or > 2^30, NULL rays or hits with n_rays > 0, unknown flag bits, reserved != 0,
  * pointers that are not 4-byte aligned.  ORT_ERR_NO_SCENE: no scene, or use_octree = 1 on a
- * scene uploaded without a tree.  Not in scope: a caller-chosen (t_min, t_max), queries on an
- * ort_group.  (A frame's camera rays: ort_trace_camera below.) */
+ * scene uploaded without a tree.  Not in scope: queries on an ort_group.  (The nearest hit, any
+ * hit and a caller-chosen (t_min, t_max): ort_trace_rays_ex below.  A frame's camera rays:
+ * ort_trace_camera.) */
 typedef struct ort_ray     { float origin[3]; float direction[3]; } ort_ray;   /* 24 bytes */
 typedef struct ort_ray_hit { float t; int32_t sphere; } ort_ray_hit;           /* 8 bytes */
 #define ORT_QUERY_SORT 1
@@ -384,6 +385,52 @@ int ort_trace_rays(ort_ctx* ctx, const ort_ray_query* q, void* stream);
 /* Duration in milliseconds of the last ort_trace_rays' kernels (the sort's included, the host
  * copies not), from HIP events on its stream.  Only valid once that stream has passed the query. */
 int ort_last_query_ms(ort_ctx* ctx, float* ms);
+
+/* ---- query modes: the nearest hit and any hit inside a per-ray interval (visibility, shadow and
+ * segment tests, probe placement) -------------------------------------------------------------------
+ * ort_trace_rays_ex is ort_trace_rays with a mode and an optional interval per ray.  Let c_k be what
+ * Sphere_hit(k, ray, t_min, t_max) accepts for sphere k alone (glsl:224-273): its near root if that
+ * lies in the open interval (t_min, t_max), else its far root if that one does; the float32
+ * operations and their order are the shader's.
+ *   ORT_QUERY_DRAWN    ort_trace_rays' record, by the same code path: bit-identical.  Takes no
+ *                      t_range: the drawn record is the shader's interval by definition.
+ *   ORT_QUERY_NEAREST  t = the minimum of c_k over all spheres, sphere = the lowest k attaining it;
+ *                      a miss is {0.0f, -1}.  use_octree = 1 and 0, every layout and every option
+ *                      value give the same record: the tree is acceleration only.
+ *   ORT_QUERY_ANY      {c_k, k} of some sphere with a hit in the interval -- the first one the walk
+ *                      finds; which one is unspecified -- or {0.0f, -1}.  Hit-or-miss is
+ *                      deterministic and equals NEAREST's.
+ * normals are allowed in both modes; in ANY they belong to the reported sphere.
+ *   t_range   NULL: (0.001f, MAXFLOAT) for every ray.  Else 2 floats per ray {t_min, t_max}, a
+ *             device pointer iff base.on_device (a host pointer is staged like the rays).  An
+ *             interval must satisfy 0 <= t_min < t_max; anything else, NaN included, is a miss
+ *             without a walk.  t_max = +inf is taken as MAXFLOAT; t_min == 0 is valid.  t is in
+ *             units of the direction's length, as in ort_trace_rays: the segment a -> b is
+ *             d = b - a with the interval (eps, 1 - eps).
+ * Zero-axis rule (NEAREST and ANY; DRAWN keeps the shader's arithmetic): on an axis where the
+ * direction component is +-0 a box constrains the ray only by min <= origin <= max, closed on both
+ * sides, and contributes (-inf, +inf) to the box's entry and exit.  The NaN of the shader's
+ * inf * 0, which makes its min/max drop a box whose plane the origin lies on exactly, is never
+ * formed, so the walk finds what brute force finds on those rays too.
+ * Degenerate rays (zero, infinite or NaN components) terminate and miss in every mode.
+ * Shared with ort_trace_rays: the stream rules, the staging of host pointers, ort_last_query_ms,
+ * the buffers (order queries of one context among themselves) and the isolation from render and
+ * accumulation state.  ORT_QUERY_SORT, ORT_OPT_KID_SKIP, ORT_OPT_EXACT_TRAVERSAL and ORT_OPT_REFILL
+ * are accepted and give the same records under every value.  n_rays == 0: ORT_OK, nothing
+ * launched.  ORT_ERR_INVALID_ARG, before anything is launched and with the outputs untouched:
+ * whatever ort_trace_rays refuses, an unknown mode, a non-zero reserved, a t_range that is not
+ * 4-byte aligned, a t_range with ORT_QUERY_DRAWN.  ORT_ERR_NO_SCENE as ort_trace_rays.  Not in
+ * scope: queries on an ort_group. */
+#define ORT_QUERY_DRAWN   0   /* ort_trace_rays' record: intersectScene(ray, 0.001, MAXFLOAT) */
+#define ORT_QUERY_NEAREST 1   /* the nearest hit inside the ray's interval */
+#define ORT_QUERY_ANY     2   /* is there a hit inside the ray's interval? (first one found) */
+typedef struct ort_ray_query_ex {
+    ort_ray_query base;       /* rays, n_rays, hits, normals, on_device, use_octree, flags, reserved */
+    const float* t_range;     /* NULL, or 2 floats per ray {t_min, t_max}; device pointer iff base.on_device */
+    int32_t mode;             /* ORT_QUERY_* */
+    int32_t reserved[3];      /* 0 */
+} ort_ray_query_ex;
+int ort_trace_rays_ex(ort_ctx* ctx, const ort_ray_query_ex* q, void* stream);
 
 /* ---- camera queries: each pixel's camera ray and what it hits (picking under the cursor, id /
  * depth / normal images, guide buffers beside a progressive preview) -----------------------------

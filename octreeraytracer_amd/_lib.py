@@ -68,6 +68,7 @@ EXPORTED_SYMBOLS = (
     "ort_accum_begin", "ort_accum_render", "ort_accum_restart", "ort_accum_get_info", "ort_accum_last_pass_ms",
     "ort_accum_free",
     "ort_trace_camera",
+    "ort_trace_rays_ex",
 )
 ORT_GROUP_TRANSPORT_RCCL = 0
 ORT_GROUP_TRANSPORT_COPY = 1
@@ -81,6 +82,11 @@ PLACEMENTS = {"tile": ORT_PLACE_TILE, "frame": ORT_PLACE_FRAME}
 FORMAT_BPP = {ORT_FORMAT_RGB32F: 12, ORT_FORMAT_RGBA8: 4}
 # ort_ray_query.flags (ort_trace_rays)
 ORT_QUERY_SORT = 1
+# ort_ray_query_ex.mode (ort_trace_rays_ex)
+ORT_QUERY_DRAWN = 0
+ORT_QUERY_NEAREST = 1
+ORT_QUERY_ANY = 2
+QUERY_MODES = {"drawn": ORT_QUERY_DRAWN, "nearest": ORT_QUERY_NEAREST, "any": ORT_QUERY_ANY}
 # ort_camera_query.which (ort_trace_camera)
 ORT_CAMERA_FIRST_SAMPLE = 0
 ORT_CAMERA_PIXEL_CENTRE = 1
@@ -122,6 +128,10 @@ class OrtRayQuery(C.Structure):
         ("rays", C.c_void_p), ("n_rays", C.c_int64), ("hits", C.c_void_p), ("normals", C.c_void_p),
         ("on_device", C.c_int32), ("use_octree", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
     ]
+
+
+class OrtRayQueryEx(C.Structure):
+    _fields_ = [("base", OrtRayQuery), ("t_range", C.c_void_p), ("mode", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class OrtCameraQuery(C.Structure):
@@ -177,6 +187,7 @@ def _declare(lib, debug: str = "none"):
         "ort_render_ex": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(OrtOutput), _vp]),
         "ort_trace_rays": (C.c_int, [_vp, C.POINTER(OrtRayQuery), _vp]),
         "ort_last_query_ms": (C.c_int, [_vp, _fp]),
+        "ort_trace_rays_ex": (C.c_int, [_vp, C.POINTER(OrtRayQueryEx), _vp]),
         "ort_trace_camera": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(OrtCameraQuery), _vp]),
         "ort_accum_begin": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(_vp)]),
         "ort_accum_render": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(OrtOutput), _vp]),
@@ -226,6 +237,8 @@ def _declare(lib, debug: str = "none"):
                                            C.c_int32, C.c_int32, _ip]),
         "ort_debug_query_rays": (C.c_int, [_fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip, C.c_int64, C.c_int32,
                                            C.c_int32, _fp, C.c_int64, _vp, _fp]),
+        "ort_debug_query_rays_ex": (C.c_int, [_fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip, C.c_int64, C.c_int32,
+                                              C.c_int32, _fp, C.c_int64, C.c_int32, _fp, _vp, _fp]),
         "ort_debug_camera_query": (C.c_int, [_fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip, C.c_int64, C.c_int32,
                                              C.POINTER(OrtParams), C.POINTER(OrtTile), C.c_int32, _fp, _vp, _fp]),
         "ort_debug_split_rays": (C.c_int, [_fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip, C.c_int64, _fp,
@@ -240,8 +253,8 @@ def _declare(lib, debug: str = "none"):
     for name, (res, args) in sig.items():
         if name.startswith("ort_debug_") and (debug == "none" or (debug == "present" and not hasattr(lib, name))):
             continue
-        if name == "ort_trace_camera" and debug == "present" and not hasattr(lib, name):
-            continue  # an ORT_LIB override of a build from before camera queries (A/B runs): calling it raises
+        if name in ("ort_trace_camera", "ort_trace_rays_ex") and debug == "present" and not hasattr(lib, name):
+            continue  # an ORT_LIB override of a build from before camera queries / query modes (A/B runs): calling it raises
         f = getattr(lib, name)
         f.restype = res
         f.argtypes = args

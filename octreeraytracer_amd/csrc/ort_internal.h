@@ -74,6 +74,14 @@ int ort_debug_query_rays(const float* sphere_center_radius, int32_t n_spheres, c
                          const int32_t* object_count, int32_t n_nodes, const int32_t* object_indices, int64_t n_indices,
                          int32_t layout, int32_t use_octree, const float* rays, int64_t n_rays, ort_ray_hit* hits,
                          float* normals);
+// TEST-ONLY: ort_trace_rays_ex on the host CPU: as ort_debug_query_rays, with the mode (ORT_QUERY_*)
+// and t_range (NULL, or 2 floats per ray) of ort_ray_query_ex -- render_core.h query_ray_mode, the
+// mode kernels' own per-ray function; ORT_QUERY_DRAWN is ort_debug_query_rays itself.
+int ort_debug_query_rays_ex(const float* sphere_center_radius, int32_t n_spheres, const float* node_min,
+                            const float* node_max, const int32_t* children_offset, const int32_t* objects_offset,
+                            const int32_t* object_count, int32_t n_nodes, const int32_t* object_indices, int64_t n_indices,
+                            int32_t layout, int32_t use_octree, const float* rays, int64_t n_rays, int32_t mode,
+                            const float* t_range, ort_ray_hit* hits, float* normals);
 // TEST-ONLY: ort_trace_camera on the host CPU: the kernels' per-pixel ray (camera_query.inc
 // camera_query_ray) for every pixel of the tile, then ort_debug_query_rays over those rays by
 // params->use_octree.  rays (6 floats), hits, normals (3 floats) per tile pixel, each may be NULL

@@ -2041,7 +2041,7 @@ struct ort_ctx {
     // ray queries (ort_trace_rays, ray_query.inc): their own buffers and counters, none of the
     // per-frame state above -- the staging of host pointers (grow-only), the defer list and the
     // {deferred count, cursor} counters, ORT_QUERY_SORT's keys and lists, the timing events
-    DevBuf q_rays, q_hits, q_normals;
+    DevBuf q_rays, q_hits, q_normals, q_trange;  // (q_trange: the staged intervals of ort_trace_rays_ex)
     DevBuf q_defer, q_sync;
     DevBuf q_keys, q_keys2, q_vals, q_list, q_temp;
     hipEvent_t qev0 = nullptr, qev1 = nullptr;
@@ -3417,7 +3417,7 @@ int ort_destroy(ort_ctx* ctx) {
                       &ctx->qlist, &ctx->qlist2, &ctx->qcount, &ctx->qtemp, &ctx->skeys, &ctx->skeys2, &ctx->svals, &ctx->key_spread,
                       &ctx->pcost, &ctx->bcost, &ctx->hbits, &ctx->hlist, &ctx->hcnt, &ctx->pplist, &ctx->ppcnt, &ctx->ppcost, &ctx->spst, &ctx->spcol, &ctx->spfix, &ctx->spfixn};
     for (DevBuf* b : pipe) free_buf(*b);
-    DevBuf* query[] = {&ctx->q_rays, &ctx->q_hits, &ctx->q_normals, &ctx->q_defer, &ctx->q_sync,
+    DevBuf* query[] = {&ctx->q_rays, &ctx->q_hits, &ctx->q_normals, &ctx->q_trange, &ctx->q_defer, &ctx->q_sync,
                        &ctx->q_keys, &ctx->q_keys2, &ctx->q_vals, &ctx->q_list, &ctx->q_temp};
     for (DevBuf* b : query) free_buf(*b);
     if (ctx->qev0) (void)hipEventDestroy(ctx->qev0);
@@ -4305,3 +4305,5 @@ int ort_debug_pop_coverage(uint64_t* hb_pops, uint64_t* sign_masks, int32_t rese
 // Camera queries (ort_trace_camera, ort_debug_camera_query): after ray_query.inc, whose walk and
 // buffers they share, and after accum.inc, so that every earlier kernel keeps its place.
 #include "camera_query.inc"
+// Query modes (ort_trace_rays_ex, ort_debug_query_rays_ex): last, so that every earlier kernel keeps its place.
+#include "ray_modes.inc"

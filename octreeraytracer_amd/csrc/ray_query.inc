@@ -294,29 +294,26 @@ int query_impl(ort_ctx* ctx, const ort_ray_query* q, void* stream) {
     return ORT_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ort_trace_rays(ort_ctx* ctx, const ort_ray_query* q, void* stream) {
-    if (!ctx) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_trace_rays: null ctx");
-    return query_impl(ctx, q, stream);
-}
-
-int ort_last_query_ms(ort_ctx* ctx, float* ms) {
-    if (!ctx || !ms) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_last_query_ms: null argument");
-    if (!ctx->q_timed) return fail(ctx, ORT_ERR_NO_SCENE, "no query launched yet");
-    HIPCHK(ctx, hipEventSynchronize(ctx->qev1));
-    HIPCHK(ctx, hipEventElapsedTime(ms, ctx->qev0, ctx->qev1));
-    return ORT_OK;
-}
-
 #if ORT_ANALYSIS
-// TEST-ONLY host emulation (ort_internal.h): query_ray on the CPU, one ray after another.
-int ort_debug_query_rays(const float* cr, int32_t n_spheres, const float* node_min, const float* node_max,
-                         const int32_t* co, const int32_t* oo, const int32_t* cnt, int32_t n_nodes, const int32_t* idx,
-                         int64_t n_indices, int32_t layout, int32_t use_octree, const float* rays, int64_t n_rays,
-                         ort_ray_hit* hits, float* normals) {
+ort::RayHit debug_query_mode(const ort::KScene& S, int mode, int qmode, const float* planes, const ort::Ray& r, float t0, float t1,
+                             ort::LocalFrames& lf, int* snode, float* stmin, bool want_normal) {
+    const bool nearest = qmode == ORT_QM_NEAREST;
+    if (mode == 0)
+        return nearest ? ort::query_ray_mode<0, ORT_QM_NEAREST>(S, planes, r, t0, t1, lf, nullptr, nullptr, want_normal)
+                       : ort::query_ray_mode<0, ORT_QM_ANY>(S, planes, r, t0, t1, lf, nullptr, nullptr, want_normal);
+    if (mode == 1)
+        return nearest ? ort::query_ray_mode<1, ORT_QM_NEAREST>(S, nullptr, r, t0, t1, lf, snode, stmin, want_normal)
+                       : ort::query_ray_mode<1, ORT_QM_ANY>(S, nullptr, r, t0, t1, lf, snode, stmin, want_normal);
+    return nearest ? ort::query_ray_mode<2, ORT_QM_NEAREST>(S, nullptr, r, t0, t1, lf, nullptr, nullptr, want_normal)
+                   : ort::query_ray_mode<2, ORT_QM_ANY>(S, nullptr, r, t0, t1, lf, nullptr, nullptr, want_normal);
+}
+
+// TEST-ONLY host emulation (ort_internal.h): query_ray on the CPU, one ray after another; with
+// qmode ORT_QM_NEAREST / ORT_QM_ANY query_ray_mode and the ray's interval (ray_modes.inc).
+int debug_query_rays(const float* cr, int32_t n_spheres, const float* node_min, const float* node_max,
+                     const int32_t* co, const int32_t* oo, const int32_t* cnt, int32_t n_nodes, const int32_t* idx,
+                     int64_t n_indices, int32_t layout, int32_t use_octree, const float* rays, int64_t n_rays,
+                     int qmode, const float* t_range, ort_ray_hit* hits, float* normals) {
     try {
         if (!cr || n_spheres <= 0 || n_rays < 0 || (n_rays > 0 && (!rays || !hits)))
             return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_query_rays: bad argument");
@@ -381,7 +378,10 @@ int ort_debug_query_rays(const float* cr, int32_t n_spheres, const float* node_m
             r.o = ort::mk(rays[6 * (size_t)i], rays[6 * (size_t)i + 1], rays[6 * (size_t)i + 2]);
             r.d = ort::mk(rays[6 * (size_t)i + 3], rays[6 * (size_t)i + 4], rays[6 * (size_t)i + 5]);
             ort::RayHit h;
-            if (mode == 0)
+            const float t0 = t_range ? t_range[2 * (size_t)i] : 0.001f, t1 = t_range ? t_range[2 * (size_t)i + 1] : ORT_MAXFLOAT;
+            if (qmode != 0)
+                h = debug_query_mode(S, mode, qmode, fplanes.data(), r, t0, t1, lf, snode.data(), stmin.data(), normals != nullptr);
+            else if (mode == 0)
                 h = ort::query_ray<0>(S, fplanes.data(), fplanes_b.data(), rank_lut, r, lf, nullptr, nullptr, normals != nullptr);
             else if (mode == 1)
                 h = ort::query_ray<1>(S, nullptr, nullptr, nullptr, r, lf, snode.data(), stmin.data(), normals != nullptr);
@@ -399,6 +399,33 @@ int ort_debug_query_rays(const float* cr, int32_t n_spheres, const float* node_m
     } catch (const std::exception& ex) {
         return fail(nullptr, ORT_ERR_INTERNAL, ex.what());
     }
+}
+#endif  // ORT_ANALYSIS
+
+}  // namespace
+
+extern "C" {
+
+int ort_trace_rays(ort_ctx* ctx, const ort_ray_query* q, void* stream) {
+    if (!ctx) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_trace_rays: null ctx");
+    return query_impl(ctx, q, stream);
+}
+
+int ort_last_query_ms(ort_ctx* ctx, float* ms) {
+    if (!ctx || !ms) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_last_query_ms: null argument");
+    if (!ctx->q_timed) return fail(ctx, ORT_ERR_NO_SCENE, "no query launched yet");
+    HIPCHK(ctx, hipEventSynchronize(ctx->qev1));
+    HIPCHK(ctx, hipEventElapsedTime(ms, ctx->qev0, ctx->qev1));
+    return ORT_OK;
+}
+
+#if ORT_ANALYSIS
+int ort_debug_query_rays(const float* cr, int32_t n_spheres, const float* node_min, const float* node_max,
+                         const int32_t* co, const int32_t* oo, const int32_t* cnt, int32_t n_nodes, const int32_t* idx,
+                         int64_t n_indices, int32_t layout, int32_t use_octree, const float* rays, int64_t n_rays,
+                         ort_ray_hit* hits, float* normals) {
+    return debug_query_rays(cr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices, layout, use_octree, rays,
+                            n_rays, 0, nullptr, hits, normals);
 }
 #endif  // ORT_ANALYSIS
 

@@ -160,6 +160,38 @@ int Raytracer::traceRays(const ort_ray* rays, int64_t n, ort_ray_hit* hits, floa
     return ort_trace_rays(ctx, &q, nullptr);
 }
 
+int Raytracer::traceRays(const ort_ray* rays, int64_t n, ort_ray_hit* hits, float* normals, int mode, const float* t_range) {
+    if (!ctx && !group && !initialize()) return ORT_ERR_HIP;
+    if (group) return ORT_ERR_UNSUPPORTED;  // queries run on one context
+    if (!sceneReady) {
+        setupScene();
+        setupBuffers();
+        if (!sceneReady) return ORT_ERR_INVALID_ARG;
+    }
+    const ort_ray_query_ex q = {{rays, n, hits, normals, 0, cfg.useOctree, 0, 0}, t_range, mode, {0, 0, 0}};
+    return ort_trace_rays_ex(ctx, &q, nullptr);
+}
+
+int Raytracer::occluded(const float* a, const float* b, int64_t n, uint8_t* out, float eps) {
+    if (n < 0 || (n > 0 && (!a || !b || !out)) || !(eps >= 0.0f)) return ORT_ERR_INVALID_ARG;
+    std::vector<ort_ray> rays((size_t)n);
+    std::vector<float> range(2 * (size_t)n);
+    std::vector<ort_ray_hit> hits((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        const float d[3] = {b[3 * i] - a[3 * i], b[3 * i + 1] - a[3 * i + 1], b[3 * i + 2] - a[3 * i + 2]};
+        const float len = std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+        const bool ok = len > 2.0f * eps;  // (NaN: not ok) -- else an empty interval: a miss
+        rays[(size_t)i] = {{a[3 * i], a[3 * i + 1], a[3 * i + 2]},
+                           {ok ? d[0] / len : 0.0f, ok ? d[1] / len : 0.0f, ok ? d[2] / len : 0.0f}};
+        range[2 * (size_t)i] = eps;
+        range[2 * (size_t)i + 1] = ok ? len - eps : 0.0f;
+    }
+    const int rc = traceRays(rays.data(), n, hits.data(), nullptr, ORT_QUERY_ANY, range.data());
+    if (rc != ORT_OK) return rc;
+    for (int64_t i = 0; i < n; ++i) out[i] = hits[(size_t)i].sphere >= 0 ? 1 : 0;
+    return ORT_OK;
+}
+
 int Raytracer::traceCamera(const Camera& cam, const ort_tile& tile, const ort_camera_query& query) {
     if (!ctx && !group && !initialize()) return ORT_ERR_HIP;
     if (group) return ORT_ERR_UNSUPPORTED;  // queries run on one context

@@ -88,6 +88,17 @@ public:
     // Host pointers; builds and uploads the scene on first use, like render.  Single-device
     // configurations only (a group: ORT_ERR_UNSUPPORTED).
     int traceRays(const ort_ray* rays, int64_t n, ort_ray_hit* hits, float* normals = nullptr);
+    // The same in a query mode (include/ort.h ort_trace_rays_ex): ORT_QUERY_NEAREST -- the nearest
+    // hit inside the ray's interval, the same with and without the octree -- or ORT_QUERY_ANY -- the
+    // first hit found inside it; t_range nullptr ((0.001, MAXFLOAT) for every ray) or 2 floats per
+    // ray {t_min, t_max} in units of the direction's length.  ORT_QUERY_DRAWN is the call above and
+    // takes no t_range.
+    int traceRays(const ort_ray* rays, int64_t n, ort_ray_hit* hits, float* normals, int mode, const float* t_range);
+    // Segment visibility: out[i] = 1 when a sphere lies strictly between the points a[3 i ..] and
+    // b[3 i ..], else 0 -- one ORT_QUERY_ANY ray per pair from a along the unit direction with the
+    // interval (eps, |b - a| - eps), formed in float32; a pair no further apart than 2 eps is not
+    // occluded.
+    int occluded(const float* a, const float* b, int64_t n, uint8_t* out, float eps = 1e-3f);
     // Camera queries (include/ort.h ort_trace_camera): for every pixel of the tile of cam's frame
     // (cfg's size, samples and walk) the camera ray the frame is drawn with and what it hits --
     // query.rays, .hits, .normals and .which as ort_camera_query describes them.  Synchronous;

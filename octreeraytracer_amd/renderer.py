@@ -341,7 +341,8 @@ class Renderer:
         return Accumulation(self, params, tile or Tile.full(params))
 
     # -- ray queries ------------------------------------------------------------------
-    def trace_rays(self, rays, *, use_octree=True, sort=False, normals=False, out=None, stream=None, n=None):
+    def trace_rays(self, rays, *, use_octree=True, sort=False, normals=False, out=None, stream=None, n=None,
+                   mode="drawn", t_range=None):
         """What does each ray hit, and where (ort_trace_rays, include/ort.h): per ray the shader's
         intersectScene(ray, 0.001, MAXFLOAT) -- t (in units of the direction's length; directions
         are used as given) and the index of the hit sphere in the uploaded arrays, (0.0, -1) for a
@@ -357,10 +358,30 @@ class Renderer:
         {t bits, sphere} (allocated when None; a pointer needs out given), and with normals the
         (n, 3) float32 normals tensor (normals=True allocates it; a tensor or pointer is used).
         sort: walk the rays in coherence order (ORT_QUERY_SORT; same records, same order).
-        stream: as render()."""
+        stream: as render().
+
+        mode: "drawn" (the above), "nearest" -- the nearest hit inside the ray's interval, the lowest
+        sphere index among equals, the same record with and without the octree -- or "any" -- some
+        sphere with a hit inside the interval, the first one found (ort_trace_rays_ex).
+        t_range: None = (0.001, MAXFLOAT) for every ray, else {t_min, t_max} per ray, in units of the
+        direction's length: with host rays a C-contiguous (n, 2) float32 array, with device rays a
+        contiguous (n, 2) float32 CUDA tensor or a device pointer.  0 <= t_min < t_max, else the ray
+        misses; not with mode="drawn", whose interval is the shader's."""
         flags = L.ORT_QUERY_SORT if sort else 0
         s = C.c_void_p(int(stream)) if stream else None
-        q = L.OrtRayQuery(None, 0, None, None, 0, 1 if use_octree else 0, flags, 0)
+        if mode not in L.QUERY_MODES:
+            raise ValueError(f"trace_rays: mode must be one of {sorted(L.QUERY_MODES)} (got {mode!r})")
+        if t_range is not None and mode == "drawn":
+            raise ValueError('trace_rays: t_range needs mode="nearest" or "any": the drawn record is the shader\'s interval')
+        ex = mode != "drawn"
+        qx = L.OrtRayQueryEx(L.OrtRayQuery(None, 0, None, None, 0, 1 if use_octree else 0, flags, 0), None,
+                             L.QUERY_MODES[mode], (C.c_int32 * 3)(0, 0, 0))
+        q = qx.base
+
+        def trace():  # the defaults call ort_trace_rays as ever
+            if ex:
+                return self._lib.ort_trace_rays_ex(self._ctx, C.byref(qx), s)
+            return self._lib.ort_trace_rays(self._ctx, C.byref(q), s)
         if isinstance(rays, np.ndarray):
             if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 6 or not rays.flags.c_contiguous:
                 raise ValueError(f"trace_rays: rays must be a C-contiguous (n, 6) float32 array (got {rays.dtype}, "
@@ -375,11 +396,17 @@ class Renderer:
                 raise ValueError(f"trace_rays: out must be a C-contiguous int32 numpy array of >= {8 * nr} bytes")
             if not isinstance(normals, (bool, np.bool_)):
                 raise ValueError("trace_rays: with host rays, normals is True or False")
+            if t_range is not None:
+                if (not isinstance(t_range, np.ndarray) or t_range.dtype != np.float32 or t_range.ndim != 2 or
+                        t_range.shape != (nr, 2) or not t_range.flags.c_contiguous):
+                    raise ValueError(f"trace_rays: with host rays, t_range must be a C-contiguous ({nr}, 2) float32 array "
+                                     f"(got {getattr(t_range, 'dtype', type(t_range))}, shape {getattr(t_range, 'shape', None)})")
+                qx.t_range = t_range.ctypes.data_as(C.c_void_p)
             nrm = np.zeros((nr, 3), np.float32) if normals else None
             q.rays, q.n_rays = rays.ctypes.data_as(C.c_void_p), nr
             q.hits = out.ctypes.data_as(C.c_void_p)
             q.normals = nrm.ctypes.data_as(C.c_void_p) if normals else None
-            self._check(self._lib.ort_trace_rays(self._ctx, C.byref(q), s))
+            self._check(trace())
             rec = out.reshape(-1)[:2 * nr].reshape(nr, 2)
             t, sph = np.ascontiguousarray(rec[:, 0]).view(np.float32), np.ascontiguousarray(rec[:, 1])
             return (t, sph, nrm) if normals else (t, sph)
@@ -420,9 +447,39 @@ class Renderer:
         want_normals = not isinstance(normals, (bool, np.bool_))
         q.hits = C.c_void_p(device_arg(out, "out", "int32", 8 * nr))
         q.normals = C.c_void_p(device_arg(normals, "normals", "float32", 12 * nr)) if want_normals else None
+        if t_range is not None:
+            if hasattr(t_range, "data_ptr") and (t_range.dim() != 2 or tuple(t_range.shape) != (nr, 2)):
+                raise ValueError(f"trace_rays: t_range must have shape ({nr}, 2) (got {tuple(t_range.shape)})")
+            qx.t_range = C.c_void_p(device_arg(t_range, "t_range", "float32", 8 * nr))
         q.on_device = 1
-        self._check(self._lib.ort_trace_rays(self._ctx, C.byref(q), s))
+        self._check(trace())
         return (out, normals) if want_normals else out
+
+    def occluded(self, origins, targets, *, eps=1e-3, use_octree=True):
+        """Segment visibility: per pair (a, b) of the (n, 3) host arrays, is any sphere hit strictly
+        between the two points?  One ORT_QUERY_ANY ray per pair from a along the unit direction
+        (b - a) / |b - a| with the interval (eps, |b - a| - eps), all formed in float32.  Returns a
+        bool array (n,); a pair with |b - a| <= 2 eps (coincident points among them) is not occluded."""
+        a = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(targets, np.float32).reshape(-1, 3)
+        if a.shape != b.shape:
+            raise ValueError(f"occluded: {a.shape[0]} origins but {b.shape[0]} targets")
+        eps = np.float32(eps)
+        if not eps >= 0:
+            raise ValueError(f"occluded: eps must be >= 0 (got {eps})")
+        d = b - a
+        with np.errstate(all="ignore"):
+            length = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).astype(np.float32)
+            ok = length > np.float32(2) * eps  # (NaN: not ok)
+            unit = np.where(ok[:, None], d / np.where(ok, length, np.float32(1))[:, None], np.float32(0)).astype(np.float32)
+        rays = np.ascontiguousarray(np.concatenate([a, unit], axis=1), np.float32)
+        t_range = np.empty((len(a), 2), np.float32)
+        t_range[:, 0] = eps
+        t_range[:, 1] = np.where(ok, length - eps, np.float32(0))  # (eps, 0) or (0, 0): an empty interval, a miss
+        if len(a) == 0:
+            return np.zeros(0, bool)
+        _, sph = self.trace_rays(rays, use_octree=use_octree, mode="any", t_range=t_range)
+        return (sph >= 0) & ok
 
     # -- camera queries ---------------------------------------------------------------
     def trace_camera(self, params: FrameParams, tile: Tile | None = None, *, which: str = "first_sample", rays=False,
@@ -695,12 +752,21 @@ def emulate_render_host(spheres: SphereSet, tree: FlatOctree | None, params: Fra
 
 
 def query_rays_host(spheres: SphereSet, tree: FlatOctree | None, rays, *, layout: int = L.ORT_LAYOUT_COMPACT,
-                    use_octree: bool = True, normals: bool = False):
+                    use_octree: bool = True, normals: bool = False, mode: str | None = None, t_range=None):
     """TEST-ONLY: ``Renderer.trace_rays`` on the host CPU (ort_debug_query_rays: render_core.h
-    query_ray, the kernels' own per-ray function).  Returns (t, sphere[, normals])."""
+    query_ray, the kernels' own per-ray function).  Returns (t, sphere[, normals]).  With mode
+    ("drawn", "nearest", "any") ort_debug_query_rays_ex: query_ray_mode over t_range, None or (n, 2)."""
     lib = L.analysis_lib()
     rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
     n = rays.shape[0]
+    if mode is not None and mode not in L.QUERY_MODES:
+        raise ValueError(f"query_rays_host: mode must be one of {sorted(L.QUERY_MODES)} (got {mode!r})")
+    if t_range is not None:
+        if mode is None or mode == "drawn":
+            raise ValueError('query_rays_host: t_range needs mode="nearest" or "any"')
+        t_range = np.ascontiguousarray(t_range, np.float32)
+        if t_range.shape != (n, 2):
+            raise ValueError(f"query_rays_host: t_range must have shape ({n}, 2) (got {t_range.shape})")
     cr = np.ascontiguousarray(spheres.center_radius, np.float32)
     if tree is None:
         keep = ()
@@ -713,8 +779,13 @@ def query_rays_host(spheres: SphereSet, tree: FlatOctree | None, rays, *, layout
                 tree.n_nodes, L.iptr(keep[5]), tree.n_indices)
     rec = np.empty((n, 2), np.int32)
     nrm = np.zeros((n, 3), np.float32) if normals else None
-    L.acheck(lib.ort_debug_query_rays(L.fptr(cr), spheres.n, *args, int(layout), 1 if use_octree else 0, L.fptr(rays), n,
-                                     rec.ctypes.data_as(C.c_void_p), L.fptr(nrm)))
+    if mode is None:
+        L.acheck(lib.ort_debug_query_rays(L.fptr(cr), spheres.n, *args, int(layout), 1 if use_octree else 0, L.fptr(rays), n,
+                                         rec.ctypes.data_as(C.c_void_p), L.fptr(nrm)))
+    else:
+        L.acheck(lib.ort_debug_query_rays_ex(L.fptr(cr), spheres.n, *args, int(layout), 1 if use_octree else 0, L.fptr(rays),
+                                            n, L.QUERY_MODES[mode], L.fptr(t_range), rec.ctypes.data_as(C.c_void_p),
+                                            L.fptr(nrm)))
     del keep
     t, sph = np.ascontiguousarray(rec[:, 0]).view(np.float32), np.ascontiguousarray(rec[:, 1])
     return (t, sph, nrm) if normals else (t, sph)
