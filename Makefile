@@ -12,7 +12,7 @@ HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -ffp-contract=off -fno-fast-ma
 HOST_SRCS := octree.cpp scene.cpp host_abi.cpp layout.cpp raytracer.cpp
 HOST_OBJS := $(addprefix $(OBJ)/,$(HOST_SRCS:.cpp=.o))
 HIP_OBJS := $(OBJ)/ort_kernel.o $(OBJ)/gpu_build.o $(OBJ)/group.o
-HDRS := $(wildcard $(SRC)/*.h) $(SRC)/prebuilt_scene.inc $(SRC)/ray_query.inc $(SRC)/accum.inc $(SRC)/camera_query.inc $(SRC)/ray_modes.inc include/ort.h include/ort_math.h
+HDRS := $(wildcard $(SRC)/*.h) $(SRC)/prebuilt_scene.inc $(SRC)/ray_query.inc $(SRC)/accum.inc $(SRC)/camera_query.inc $(SRC)/ray_modes.inc $(SRC)/host_emulation.inc include/ort.h include/ort_math.h
 
 # The analysis library (test/analysis surface: ort_debug_* host emulation and walk statistics,
 # ORT_OPT_DEBUG_FLAGS) -- the same sources with -DORT_ANALYSIS=1; the CPU suite and tools/

@@ -1,9 +1,11 @@
 // camera_query.inc -- camera queries (ort_trace_camera): per tile pixel the camera ray the shader
 // makes for it and what that ray hits, {ray, t, sphere[, normal]} records.
 // Included by ort_kernel.hip after ray_query.inc (its kernels follow the query kernels in the code
-// object, whose code is unchanged); shares the queries' buffers, counters and events (ort_ctx::q_*).
-//   ort_camera_rays<DEEP>  compact layout: ort_query_rays' persistent walk; at refill a lane makes
-//                          its pixel's ray in registers instead of loading a caller's
+// object, whose code is unchanged).  ort_camera_lane is ray_query.inc's query_lane_body over
+// CameraSource; ort_camera_rays keeps its own copy of the loop (see there).  The host side is ray_query.inc's staging (query_begin / query_start /
+// query_finish) and state (ort_ctx::query).
+//   ort_camera_rays<DEEP>  compact layout: at refill a lane makes its pixel's ray in registers
+//                          instead of loading a caller's
 //   ort_camera_exact       the literal exact walk of the deferred pixels (the ray made again)
 //   ort_camera_lane<MODE>  explicit layout (1) and brute force (2): one pixel per lane
 //   ort_camera_gen         ray generation only (hits == NULL): a plain grid
@@ -73,10 +75,29 @@ __device__ inline void camera_store_empty(const CameraArgs& A, int i) {
     if (A.q.hits) query_store(A.q, i, ort::query_hit<0>(A.q.S, zero, false, 0.0f, -1, false));
 }
 
-// ort_query_rays with the ray made at refill: the same loop, chunks, refill threshold, leaf hold
-// and walk configuration (Masks64Plain at depth <= 8, Masks96Lean over the reversed tables at
-// depth 9-10).  The ray lives in registers from camera_item_ray to fast_begin and is stored only
-// where the caller asked for rays; the walk state gives it back for the record (st.ray()).
+// The camera's pixels as ray_query.inc's item source: the work item is the record index, the ray
+// is made in registers and stored only where the caller asked for rays; a row past the frame gets
+// its empty record here.
+struct CameraSource {
+    const CameraArgs& A;
+    __device__ __forceinline__ int index(int pos) const { return pos; }
+    __device__ __forceinline__ bool item(int i, ort::Ray& ray) const {
+        if (!camera_item_ray(A, i, ray)) {
+            camera_store_empty(A, i);
+            return false;
+        }
+        if (A.rays_out) camera_store_ray(A, i, ray);
+        return true;
+    }
+};
+
+// NOT folded into ray_query.inc's query_item_loop: over CameraSource with FastQueryWalk the compiler
+// spills more (104-124 B of scratch against this body's 100 B at the same 80 VGPRs:
+// profiles/query_refactor/resource_usage.md), so this kernel keeps its own copy of the loop --
+// ort_query_rays' with the ray made at refill: the same chunks, refill threshold, leaf hold and walk
+// configuration.  A change to query_item_loop is made here too.  The ray lives in registers from
+// camera_item_ray to fast_begin and is stored only where the caller asked for rays; the walk state
+// gives it back for the record (st.ray()).
 template <bool DEEP>
 __global__ void __launch_bounds__(DEEP ? kPersistDeepBlock : kBlock) __attribute__((amdgpu_waves_per_eu(ORT_PERSISTENT_WAVES)))
 ort_camera_rays(CameraArgs A) {
@@ -176,26 +197,11 @@ __global__ void __launch_bounds__(kBlock) ort_camera_exact(CameraArgs A) {
     }
 }
 
-// One pixel per lane: the explicit layout's literal stack walk (MODE 1), brute force (2).
 template <int MODE>
 __global__ void __launch_bounds__(kBlock) ort_camera_lane(CameraArgs A) {
-    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= A.q.n) return;
-    ort::Ray ray;
-    if (!camera_item_ray(A, (int)i, ray)) {
-        camera_store_empty(A, (int)i);
-        return;
-    }
-    if (A.rays_out) camera_store_ray(A, (int)i, ray);
-    const bool want_normal = A.q.normals != nullptr;
-    ort::LocalFrames unused;
-    if constexpr (MODE == 1) {
-        int snode[ORT_MAX_STACK];
-        float stmin[ORT_MAX_STACK];
-        query_store(A.q, (int)i, ort::query_ray<1>(A.q.S, nullptr, nullptr, nullptr, ray, unused, snode, stmin, want_normal));
-    } else {
-        query_store(A.q, (int)i, ort::query_ray<2>(A.q.S, nullptr, nullptr, nullptr, ray, unused, nullptr, nullptr, want_normal));
-    }
+    query_lane_body<MODE>(A.q, CameraSource{A}, [&](const ort::Ray& ray, int, ort::LocalFrames& lf, int* snode, float* stmin, bool want_normal) {
+        return ort::query_ray<MODE>(A.q.S, nullptr, nullptr, nullptr, ray, lf, snode, stmin, want_normal);
+    });
 }
 
 // Ray generation only: nothing is walked, no scene is read (A.q.hits is null).
@@ -228,79 +234,30 @@ int camera_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, const ort_
     const std::string bad = check_camera_query(p, t, q);
     if (!bad.empty()) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_trace_camera: " + bad);
     const bool walk = q->hits != nullptr;
-    int mode = 2;
-    if (walk) {
-        if (!ctx->has_scene) return fail(ctx, ORT_ERR_NO_SCENE, "ort_trace_camera: no scene uploaded");
-        mode = (p->use_octree == 1) ? (ctx->layout == ORT_LAYOUT_COMPACT ? 0 : 1) : 2;
-        if (mode != 2 && ctx->n_nodes <= 0) return fail(ctx, ORT_ERR_NO_SCENE, "ort_trace_camera: scene has no octree");
-    }
-    const size_t n = (size_t)t->width * (size_t)t->rows;
-    if (n == 0) return ORT_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    const bool host = !q->on_device;
-    int rc;
-    if ((rc = ensure(ctx, ctx->q_sync, 64))) return rc;
-    if (walk && mode == 0 && (rc = ensure(ctx, ctx->q_defer, 4 * n))) return rc;
-    if (host && ((q->rays && (rc = ensure(ctx, ctx->q_rays, sizeof(ort_ray) * n))) ||
-                 (walk && (rc = ensure(ctx, ctx->q_hits, sizeof(ort_ray_hit) * n))) ||
-                 (q->normals && (rc = ensure(ctx, ctx->q_normals, 12 * n)))))
-        return rc;
-    if (!ctx->qev0) HIPCHK(ctx, hipEventCreate(&ctx->qev0));
-    if (!ctx->qev1) HIPCHK(ctx, hipEventCreate(&ctx->qev1));
+    QueryCall c;
     CameraArgs a;
     std::memset(&a, 0, sizeof(a));
-    if (walk) {
-        a.q.S = device_scene(ctx);
-        a.q.hits = host ? (int2*)ctx->q_hits.p : (int2*)q->hits;
-        a.q.normals = q->normals ? (host ? (float*)ctx->q_normals.p : q->normals) : nullptr;
-        a.q.defer_list = (int*)ctx->q_defer.p;
-    }
-    a.q.sync = (int*)ctx->q_sync.p;
-    a.q.n = (int)n;
-    a.q.refill = ctx->refill;
-    a.q.exact_only = ctx->exact_only || !ctx->ordered;
+    const QueryIo io = {nullptr, q->rays, q->hits, q->normals, q->on_device != 0, false, true};
+    int rc = query_begin(ctx, "ort_trace_camera", walk, p->use_octree, (size_t)t->width * (size_t)t->rows, io, stream, c, a.q);
+    if (rc || c.n == 0) return rc;
     a.pp = pixel_params(p);
     a.tm = {t->x0, t->width, t->y0, t->rows, t->band_height, t->band_stride};
-    a.rays_out = q->rays ? (host ? (float*)ctx->q_rays.p : (float*)q->rays) : nullptr;
+    a.rays_out = q->rays ? (c.host ? (float*)ctx->query.rays.p : (float*)q->rays) : nullptr;
     a.which = q->which;
-    HIPCHK(ctx, hipMemsetAsync(ctx->q_sync.p, 0, 64, s));
-    HIPCHK(ctx, hipEventRecord(ctx->qev0, s));
+    if ((rc = query_start(ctx, c, a.q))) return rc;
     hipError_t e;
-    const long long blocks = ((long long)n + kBlock - 1) / kBlock;
     if (!walk) {
-        hipLaunchKernelGGL(ort_camera_gen, dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+        hipLaunchKernelGGL(ort_camera_gen, dim3((unsigned)c.blocks), dim3(kBlock), 0, c.s, a);
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, "ort_camera_gen launch");
-    } else if (mode == 0) {
-        const bool deep = ctx->depth > 8;
-        const size_t lds = deep ? lds_bytes(0, ctx->depth, false, kRevBounce, kPersistDeepBlock) : lds_bytes(0, ctx->depth, false);
-        if (deep) {
-            const int g = resident_blocks(ctx->device, ort_camera_rays<true>, kPersistDeepBlock, lds, blocks);
-            hipLaunchKernelGGL((ort_camera_rays<true>), dim3(g), dim3(kPersistDeepBlock), lds, s, a);
-        } else {
-            const int g = resident_blocks(ctx->device, ort_camera_rays<false>, kBlock, lds, blocks);
-            hipLaunchKernelGGL((ort_camera_rays<false>), dim3(g), dim3(kBlock), lds, s, a);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, "ort_camera_rays launch");
-        hipLaunchKernelGGL(ort_camera_exact, dim3((unsigned)std::min<long long>(blocks, 256)), dim3(kBlock),
-                           lds_bytes(0, ctx->depth, true), s, a);
-        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, "ort_camera_exact launch");
+    } else if (c.mode == 0) {
+        if ((rc = launch_fast_walk(ctx, c, a, ort_camera_rays<true>, ort_camera_rays<false>, ort_camera_exact, "ort_camera"))) return rc;
     } else {
-        if (mode == 1) hipLaunchKernelGGL((ort_camera_lane<1>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((ort_camera_lane<2>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+        pick<1, 2>(c.mode, [&](auto MODE) {
+            hipLaunchKernelGGL((ort_camera_lane<ORT_V(MODE)>), dim3((unsigned)c.blocks), dim3(kBlock), 0, c.s, a);
+        });
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, "ort_camera_lane launch");
     }
-    HIPCHK(ctx, hipEventRecord(ctx->qev1, s));
-    ctx->q_timed = true;
-    if (host) {
-        if (q->rays) HIPCHK(ctx, hipMemcpyAsync(q->rays, ctx->q_rays.p, sizeof(ort_ray) * n, hipMemcpyDeviceToHost, s));
-        if (walk) HIPCHK(ctx, hipMemcpyAsync(q->hits, ctx->q_hits.p, sizeof(ort_ray_hit) * n, hipMemcpyDeviceToHost, s));
-        if (q->normals) HIPCHK(ctx, hipMemcpyAsync(q->normals, ctx->q_normals.p, 12 * n, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-    } else if (!stream) {
-        HIPCHK(ctx, hipStreamSynchronize(s));
-    }
-    return ORT_OK;
+    return query_finish(ctx, c);
 }
 
 }  // namespace

@@ -1,0 +1,589 @@
+// host_emulation.inc -- the TEST-ONLY host emulation (ort_internal.h: ort_debug_*), included by
+// ort_kernel.hip in analysis builds (ORT_ANALYSIS) only: the kernels' per-ray and per-pixel code of
+// render_core.h run on the CPU, the yardstick of the CPU suite.  Host code only.  Every emulation
+// walks a HostScene; the queries' emulations (ray_query.inc, camera_query.inc, ray_modes.inc) too.
+
+namespace {
+
+// The scene a host emulation walks, built once from the raw arrays as the upload builds the
+// device's: the compact layout with the fast walks' plane tables (fplanes; fplanes_b: the bounce
+// walk's, reversed at depth 9-10) and the rank LUT, or the explicit layout's node arrays, or
+// nothing more for brute force; with materials (ma, fr) or without (null).  The KScene points
+// into this object: it is neither copied nor moved.
+struct HostScene {
+    enum Check {
+        kValidate = 1,      // validateScene first, whatever the mode
+        kNoOctree = 2,      // a tree walk of a scene without nodes: ORT_ERR_NO_SCENE "no octree"
+        kValidateTree = 4,  // validateScene for a tree walk only, after kNoOctree
+        kOrdered = 8,       // an unordered tree: ORT_ERR_UNSUPPORTED "unordered tree"
+    };
+    ort::KScene S;
+    int mode = 2;  // 0 compact, 1 explicit, 2 brute force
+    ort::CompactLayout cl;
+    std::vector<float> fplanes, fplanes_b;
+    std::vector<uint8_t> lut;           // the rank LUT
+    const uint8_t* rank_lut = nullptr;  // ... null for an unordered tree (and without the compact layout)
+    std::string error;                  // of a failed build
+    HostScene() { std::memset(&S, 0, sizeof(S)); }
+    HostScene(const HostScene&) = delete;
+    HostScene& operator=(const HostScene&) = delete;
+
+    // use_octree != 1: brute force.  Returns ORT_OK or the code to fail with (text in `error`).
+    int build(const float* cr, const float* ma, const float* fr, int32_t n_spheres, const float* node_min, const float* node_max,
+              const int32_t* co, const int32_t* oo, const int32_t* cnt, int32_t n_nodes, const int32_t* idx, int64_t n_indices,
+              int32_t layout, int32_t use_octree, int checks) {
+        if (!ma || !fr) zeros_.assign((size_t)n_spheres * 4, 0.0f);
+        const ort::SceneInput in{cr, ma ? ma : zeros_.data(), fr ? fr : zeros_.data(), n_spheres, node_min, node_max, co, oo, cnt,
+                                 n_nodes, idx, n_indices};
+        const bool tree = use_octree == 1;
+        if (checks & kValidate) error = ort::validateScene(in);
+        if (!error.empty()) return ORT_ERR_INVALID_ARG;
+        if (tree && (checks & kNoOctree) && n_nodes <= 0) return error = "no octree", ORT_ERR_NO_SCENE;
+        if (tree && (checks & kValidateTree)) error = ort::validateScene(in);
+        if (!error.empty()) return ORT_ERR_INVALID_ARG;
+        S.sph_cr = (const float4*)cr;
+        if (ma && fr) {
+            fr2_.resize((size_t)n_spheres * 2);
+            for (int32_t i = 0; i < n_spheres; ++i) {
+                fr2_[2 * (size_t)i] = fr[4 * (size_t)i];
+                fr2_[2 * (size_t)i + 1] = fr[4 * (size_t)i + 1];
+            }
+            S.sph_ma = (const float4*)ma;
+            S.sph_fr = (const float2*)fr2_.data();
+        }
+        S.n_spheres = n_spheres;
+        S.n_nodes = n_nodes;
+        lut.resize(kRankLutBytes);
+        for (size_t i = 0; i < lut.size(); ++i) lut[i] = ort::rank_lut_entry((uint32_t)i >> 8, (uint32_t)i & 255u);
+        if (!tree) return ORT_OK;
+        if (layout == ORT_LAYOUT_COMPACT) {
+            if (!ort::buildCompactLayout(in, ORT_COMPACT_MAX_DEPTH, cl, error)) return ORT_ERR_UNSUPPORTED;
+            if ((checks & kOrdered) && !cl.ordered) return error = "unordered tree", ORT_ERR_UNSUPPORTED;
+            mode = 0;
+            S.node = (const uint2*)cl.node.data();
+            S.kid = (const uint2*)cl.kid.data();
+            S.tail_base = (uint32_t)in.n_indices;
+            S.leaf_sph = (const float4*)cl.leaf_sph.data();
+            S.leaf_idx = cl.leaf_idx.data();
+            S.planes = cl.planes.data();
+            S.depth = cl.depth;
+            fplanes.resize(ort::fast_plane_floats(cl.depth));
+            ort::fill_fast_planes(cl.planes.data(), fplanes.data(), cl.depth);
+            const bool rev_b = ort::Masks96Lean::kRevPlanes || ort::fast_rev_planes(cl.depth);
+            fplanes_b.resize(ort::fast_plane_floats(cl.depth, rev_b));
+            ort::fill_fast_planes(cl.planes.data(), fplanes_b.data(), cl.depth, rev_b);
+            if (cl.ordered) rank_lut = lut.data();
+            return ORT_OK;
+        }
+        mode = 1;
+        a_.resize(4 * (size_t)n_nodes);
+        b_.resize(4 * (size_t)n_nodes);
+        for (int32_t i = 0; i < n_nodes; ++i) {
+            for (int k = 0; k < 3; ++k) {
+                a_[4 * (size_t)i + k] = node_min[3 * (size_t)i + k];
+                b_[4 * (size_t)i + k] = node_max[3 * (size_t)i + k];
+            }
+            std::memcpy(&a_[4 * (size_t)i + 3], &co[i], 4);
+            std::memcpy(&b_[4 * (size_t)i + 3], &oo[i], 4);
+        }
+        S.nodeA = (const float4*)a_.data();
+        S.nodeB = (const float4*)b_.data();
+        S.count = cnt;
+        S.indices = idx;
+        return ORT_OK;
+    }
+
+private:
+    std::vector<float> zeros_, fr2_, a_, b_;  // absent materials; the frame pairs; the explicit layout's node arrays
+};
+
+}  // namespace
+
+extern "C" {
+
+// ---- TEST-ONLY host emulation (see ort_internal.h) ----------------------------------
+int ort_debug_trace_rays(const float* cr, int32_t n_spheres, const float* node_min, const float* node_max,
+                         const int32_t* co, const int32_t* oo, const int32_t* cnt, int32_t n_nodes, const int32_t* idx,
+                         int64_t n_indices, const float* rays, int32_t n_rays, int32_t bounce, int32_t* out) {
+    try {
+        HostScene hs;
+        if (int rc = hs.build(cr, nullptr, nullptr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices,
+                              ORT_LAYOUT_COMPACT, 1, HostScene::kValidate | HostScene::kOrdered))
+            return fail(nullptr, rc, hs.error);
+        const ort::KScene& S = hs.S;
+        const std::vector<float>&fplanes = hs.fplanes, &fplanes_b = hs.fplanes_b;
+        const std::vector<uint8_t>& lut = hs.lut;
+        ort::LocalFrames lf;
+        for (int32_t i = 0; i < n_rays; ++i) {
+            ort::Ray r;
+            r.o = ort::mk(rays[6 * (size_t)i], rays[6 * (size_t)i + 1], rays[6 * (size_t)i + 2]);
+            r.d = ort::mk(rays[6 * (size_t)i + 3], rays[6 * (size_t)i + 4], rays[6 * (size_t)i + 5]);
+            ort::Counters cc;
+            for (int k = 0; k < 6; ++k) cc.v[k] = 0;
+            float tf = 0.0f, tx = 0.0f;
+            int ef = -1, ex = -1;
+            // the kernels' choice: the fast walk when fast_prepare takes the ray, else deferred
+            ort::V3 inv = ort::mk(1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z);
+            const bool fast = ort::fast_prepare(S, r, inv);
+            if (fast) {
+                if (!bounce) ort::traverse_fast<false>(S, fplanes.data(), lut.data(), r, inv, 0.001f, ORT_MAXFLOAT, ef, tf, lf, cc);
+                else if (S.depth <= 8)
+                    ort::traverse_fast_t<false, ort::Masks64Plain>(S, fplanes.data(), lut.data(), r, inv, 0.001f, ORT_MAXFLOAT,
+                                                                 ef, tf, lf, cc);
+                else
+                    ort::traverse_fast_t<false, ort::Masks96Lean>(S, fplanes_b.data(), lut.data(), r, inv, 0.001f,
+                                                                ORT_MAXFLOAT, ef, tf, lf, cc);
+            }
+            ort::traverse_compact<false>(S, fplanes.data(), r, 0.001f, ORT_MAXFLOAT, ex, tx, lf, cc);
+            int32_t* o = out + 5 * (size_t)i;
+            o[0] = fast ? 1 : 0;
+            o[1] = ef;
+            o[2] = (int32_t)ort::f2u(tf);
+            o[3] = ex;
+            o[4] = (int32_t)ort::f2u(tx);
+        }
+        return ORT_OK;
+    } catch (const std::exception& ex) {
+        return fail(nullptr, ORT_ERR_INTERNAL, ex.what());
+    }
+}
+
+int ort_debug_split_rays(const float* cr, int32_t n_spheres, const float* node_min, const float* node_max,
+                         const int32_t* co, const int32_t* oo, const int32_t* cnt, int32_t n_nodes, const int32_t* idx,
+                         int64_t n_indices, const float* rays, int32_t n_rays, int32_t level, int32_t lanes, int32_t* out) {
+    try {
+        if (lanes < 1 || level < 1) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_split_rays: lanes, level >= 1");
+        HostScene hs;
+        if (int rc = hs.build(cr, nullptr, nullptr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices,
+                              ORT_LAYOUT_COMPACT, 1, HostScene::kValidate | HostScene::kOrdered))
+            return fail(nullptr, rc, hs.error);
+        const ort::KScene& S = hs.S;
+        const std::vector<float>& fplanes = hs.fplanes;  // the default image's layout
+        const std::vector<uint8_t>& lut = hs.lut;
+        ort::LocalFrames lf;
+        for (int32_t i = 0; i < n_rays; ++i) {
+            ort::Ray r;
+            r.o = ort::mk(rays[6 * (size_t)i], rays[6 * (size_t)i + 1], rays[6 * (size_t)i + 2]);
+            r.d = ort::mk(rays[6 * (size_t)i + 3], rays[6 * (size_t)i + 4], rays[6 * (size_t)i + 5]);
+            const ort::V3 inv = ort::mk(1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z);
+            int32_t* o = out + 4 * (size_t)i;
+            o[0] = -1;
+            o[1] = 0;
+            o[2] = 0x7fffffff;
+            o[3] = 0;
+            if (!ort::fast_path_ok(r, inv, 0.001f, ORT_MAXFLOAT)) continue;
+            // the lanes of one group one after another; the lowest DFS position wins
+            int best = 0x7fffffff, be = -1, top = 0, owns = 0;  // steps as ort_trace_split records them
+            float bt = 0.0f;
+            for (int j = 0; j < lanes; ++j) {
+                int pos = 0x7fffffff, e = -1, st = 0, own = 0;
+                float t = 0.0f;
+                if (S.depth > 8)
+                    ort::traverse_split<ort::Masks96Split>(S, fplanes.data(), lut.data(), r, inv, level, lanes, j, pos, e, t, lf, st, own);
+                else
+                    ort::traverse_split<ort::Masks64Split>(S, fplanes.data(), lut.data(), r, inv, level, lanes, j, pos, e, t, lf, st, own);
+                top = std::max(top, st - own);
+                owns += own;
+                if (pos < best) {
+                    best = pos;
+                    be = e;
+                    bt = t;
+                }
+            }
+            o[0] = be;
+            o[1] = (int32_t)ort::f2u(bt);
+            o[2] = best;
+            o[3] = top + owns;
+        }
+        return ORT_OK;
+    } catch (const std::exception& ex) {
+        return fail(nullptr, ORT_ERR_INTERNAL, ex.what());
+    }
+}
+
+int ort_debug_pack_rgba8(const float* rgb, int64_t n_pixels, uint32_t* out) {
+    if (!rgb || !out || n_pixels < 0) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_pack_rgba8: null argument");
+    for (int64_t i = 0; i < n_pixels; ++i) out[i] = ort::pack_rgba8(ort::mk(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]));
+    return ORT_OK;
+}
+
+int ort_debug_fast_order(int32_t m, int32_t* order8, uint8_t* lut256) {
+    if (m < 0 || m > 7 || !order8) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_fast_order: m in 0..7");
+    for (uint32_t r = 0; r < 8; ++r) order8[r] = (int32_t)ort::rank_perm(r, (uint32_t)m);
+    if (lut256)
+        for (uint32_t c = 0; c < 256; ++c) lut256[c] = ort::rank_lut_entry((uint32_t)m, c);
+    return ORT_OK;
+}
+
+int ort_debug_emulate_render(const float* cr, const float* ma, const float* fr, int32_t n_spheres,
+                             const float* node_min, const float* node_max, const int32_t* co, const int32_t* oo,
+                             const int32_t* cnt, int32_t n_nodes, const int32_t* idx, int64_t n_indices,
+                             int32_t layout, const ort_params* p, const ort_tile* t, float* out, uint64_t* counts) {
+    return ort_debug_emulate_render_prefix(cr, ma, fr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices,
+                                           layout, p, t, -1, out, counts);
+}
+
+int ort_debug_emulate_render_prefix(const float* cr, const float* ma, const float* fr, int32_t n_spheres,
+                                    const float* node_min, const float* node_max, const int32_t* co, const int32_t* oo,
+                                    const int32_t* cnt, int32_t n_nodes, const int32_t* idx, int64_t n_indices,
+                                    int32_t layout, const ort_params* p, const ort_tile* t, int32_t samples_done,
+                                    float* out, uint64_t* counts) {
+    try {
+        const std::string bad = check_frame_tile(p, t);
+        if (!bad.empty()) return fail(nullptr, ORT_ERR_INVALID_ARG, bad);
+        if (samples_done >= 0 && (samples_done < 1 || samples_done > p->num_samples))
+            return fail(nullptr, ORT_ERR_INVALID_ARG, "samples_done must be 1 .. num_samples");
+        const int done = samples_done < 0 ? -1 : samples_done;
+        HostScene hs;  // (layout 2: the compact layout without the rank LUT)
+        if (int rc = hs.build(cr, ma, fr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices,
+                              layout == 2 ? ORT_LAYOUT_COMPACT : layout, p->use_octree, HostScene::kValidate | HostScene::kNoOctree))
+            return fail(nullptr, rc, hs.error);
+        const ort::KScene& S = hs.S;
+        const std::vector<float>&fplanes = hs.fplanes, &fplanes_b = hs.fplanes_b;
+        const int mode = hs.mode;
+        const ort::PixelParams pp = pixel_params(p);
+        const TileMap tm = {t->x0, t->width, t->y0, t->rows, t->band_height, t->band_stride};
+        ort::Counters total;
+        for (int k = 0; k < 6; ++k) total.v[k] = 0;
+        const uint8_t* rank_lut = layout == ORT_LAYOUT_COMPACT ? hs.rank_lut : nullptr;
+        std::vector<int> snode(ORT_MAX_STACK);
+        std::vector<float> stmin(ORT_MAX_STACK);
+        ort::LocalFrames lf;
+        for (int row = 0; row < t->rows; ++row) {
+            const int y = tile_row_to_y(tm, row);
+            for (int c = 0; c < t->width; ++c) {
+                float* o = out + 3 * ((size_t)row * t->width + c);
+                if (y >= p->height) { o[0] = o[1] = o[2] = 0.0f; continue; }
+                ort::Counters cc;
+                for (int k = 0; k < 6; ++k) cc.v[k] = 0;
+                ort::V3 v, vc;
+                // pixels from the production walk (COUNT=false: with the rejected-sphere skip),
+                // counters from the counting walk (the reference's work, no skip) -- and the two
+                // pixels must agree bit for bit
+                if (mode == 0) {
+                    v = ort::shade_pixel<0, false>(pp, S, fplanes.data(), fplanes_b.data(), rank_lut, lf, nullptr, nullptr,
+                                                   t->x0 + c, y, cc, done);
+                    vc = ort::shade_pixel<0, true>(pp, S, fplanes.data(), fplanes_b.data(), rank_lut, lf, nullptr, nullptr,
+                                                   t->x0 + c, y, cc, done);
+                } else if (mode == 1) {
+                    v = ort::shade_pixel<1, false>(pp, S, nullptr, nullptr, nullptr, lf, snode.data(), stmin.data(), t->x0 + c, y, cc, done);
+                    vc = ort::shade_pixel<1, true>(pp, S, nullptr, nullptr, nullptr, lf, snode.data(), stmin.data(), t->x0 + c, y, cc, done);
+                } else {
+                    v = ort::shade_pixel<2, false>(pp, S, nullptr, nullptr, nullptr, lf, nullptr, nullptr, t->x0 + c, y, cc, done);
+                    vc = ort::shade_pixel<2, true>(pp, S, nullptr, nullptr, nullptr, lf, nullptr, nullptr, t->x0 + c, y, cc, done);
+                }
+                if (ort::f2u(v.x) != ort::f2u(vc.x) || ort::f2u(v.y) != ort::f2u(vc.y) || ort::f2u(v.z) != ort::f2u(vc.z))
+                    return fail(nullptr, ORT_ERR_INTERNAL, "emulation: production and counting walks differ at pixel (" +
+                                                               std::to_string(t->x0 + c) + ", " + std::to_string(y) + ")");
+                o[0] = v.x; o[1] = v.y; o[2] = v.z;
+                cc.v[4] = 1;
+                for (int k = 0; k < 6; ++k) total.v[k] += cc.v[k];
+            }
+        }
+        if (counts) for (int k = 0; k < 6; ++k) counts[k] = total.v[k];
+        return ORT_OK;
+    } catch (const std::exception& ex) {
+        return fail(nullptr, ORT_ERR_INTERNAL, ex.what());
+    }
+}
+
+
+// Analysis builds only (ORT_PERSIST_CLOCK, tools/persist_clock.py): the persistent bounce
+// kernel records a per-wave timeline {start, queue drained, end, XCC id | items << 8} into dev
+// (n records of 4 x u64, one range per launch of a frame); null = off.
+int ort_debug_wave_clock(ort_ctx* ctx, void* dev, int64_t n) {
+    if (!ctx) return ORT_ERR_INVALID_ARG;
+    ctx->wclock = dev;
+    ctx->wclock_n = dev ? n : 0;
+    return ORT_OK;
+}
+
+// ANALYSIS-ONLY (tools/wave_stats.py): walks sampled 8x8 pixel blocks (one wave each) of
+// the primary-ray frame with the kernel's fast walk on the host and reports how the lanes'
+// visited-node sets overlap, to price wave-level (packet) traversal against the per-lane
+// loop.  stats: see tools/wave_stats.py for the field order.
+int ort_debug_wave_stats(const float* cr, const float* ma, const float* fr, int32_t n_spheres,
+                         const float* node_min, const float* node_max, const int32_t* co, const int32_t* oo,
+                         const int32_t* cnt, int32_t n_nodes, const int32_t* idx, int64_t n_indices,
+                         const ort_params* p, int32_t block_step, double* stats, int32_t n_stats) {
+    try {
+        if (n_stats < 16 || block_step < 1) return fail(nullptr, ORT_ERR_INVALID_ARG, "bad stats args");
+        HostScene hs;
+        if (int rc = hs.build(cr, ma, fr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices, ORT_LAYOUT_COMPACT, 1, 0))
+            return fail(nullptr, rc, hs.error);
+        const ort::KScene& S = hs.S;
+        const ort::CompactLayout& cl = hs.cl;
+        const std::vector<float>& fplanes = hs.fplanes;
+        const std::vector<uint8_t>& lut = hs.lut;
+        const ort::PixelParams pp = pixel_params(p);
+        ort::LocalFrames lf;
+        ort::Counters cc;
+        for (int k = 0; k < 6; ++k) cc.v[k] = 0;
+        for (int k = 0; k < n_stats; ++k) stats[k] = 0.0;
+        const int bw = (p->width + 7) / 8, bh = (p->height + 7) / 8;
+        std::vector<std::vector<int>> seq(64);
+        std::vector<int> all;
+        for (int b = 0; b < bw * bh; b += block_step) {
+            const int bx = b % bw, by = b / bw;
+            bool uniform = true;
+            int m0 = -1, lanes = 0;
+            size_t maxlen = 0;
+            for (int l = 0; l < 64; ++l) {
+                seq[l].clear();
+                const int px = bx * 8 + (l & 7), py = by * 8 + (l >> 3);
+                if (px >= p->width || py >= p->height) continue;
+                ort_rng st;
+                ort::pixel_rng_init(pp, px, py, st);
+                const ort::Ray ray = ort::primary_ray(pp, px, py, 0, st);
+                const ort::V3 inv = ort::mk(1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z);
+                if (!ort::fast_path_ok(ray, inv, 0.001f, ORT_MAXFLOAT)) { uniform = false; continue; }
+                lanes++;
+                const int m = ((ray.d.z < 0.0f) << 2) | ((ray.d.x < 0.0f) << 1) | (ray.d.y < 0.0f);
+                if (m0 < 0) m0 = m;
+                else if (m != m0) uniform = false;
+                ort::FastStateT<ort::Masks96> fs;
+                if (!ort::fast_begin(S, fplanes.data(), lut.data(), ray, inv, 0.001f, ORT_MAXFLOAT, fs)) continue;
+                for (;;) {
+                    seq[l].push_back(fs.node);
+                    if (ort::fast_step<false>(S, lut.data(), fs, lf, cc)) break;
+                }
+                maxlen = std::max(maxlen, seq[l].size());
+            }
+            stats[0] += 1;                  // waves
+            stats[1] += uniform ? 0 : 1;    // waves with mixed order / non-fast lanes
+            stats[2] += lanes;
+            all.clear();
+            for (int l = 0; l < 64; ++l)
+                for (int nd : seq[l]) {
+                    const bool leaf = !(cl.node[2 * (size_t)nd + 1] & ORT_INTERNAL_FLAG);
+                    stats[leaf ? 4 : 3] += 1;  // individual internal / leaf visits
+                    if (leaf) stats[5] += cl.node[2 * (size_t)nd + 1];  // individual sphere tests
+                    all.push_back(nd);
+                }
+            std::sort(all.begin(), all.end());
+            all.erase(std::unique(all.begin(), all.end()), all.end());
+            for (int nd : all) {
+                const bool leaf = !(cl.node[2 * (size_t)nd + 1] & ORT_INTERNAL_FLAG);
+                stats[leaf ? 7 : 6] += 1;  // union internal / leaf visits
+                if (leaf) stats[8] += cl.node[2 * (size_t)nd + 1];
+            }
+            // lockstep per-lane loop (the current kernel): iteration k runs the internal
+            // block if any lane's k-th node is internal, the leaf block (max spheres) if any
+            // is a leaf, and the pop for every lane still walking
+            for (size_t k = 0; k < maxlen; ++k) {
+                bool anyI = false, anyL = false;
+                uint32_t maxS = 0;
+                int act = 0;
+                for (int l = 0; l < 64; ++l) {
+                    if (k >= seq[l].size()) continue;
+                    act++;
+                    const uint32_t y = cl.node[2 * (size_t)seq[l][k] + 1];
+                    if (y & ORT_INTERNAL_FLAG) anyI = true;
+                    else { anyL = true; maxS = std::max(maxS, y); }
+                }
+                stats[9] += 1;            // lockstep iterations
+                stats[10] += anyI;        // iterations running the internal block
+                stats[11] += anyL;        // iterations running the leaf block
+                stats[12] += maxS;        // sphere-loop trips
+                stats[13] += act;         // lane-iterations
+            }
+            stats[14] += (double)maxlen;
+            if (n_stats >= 18) {
+                // wave-uniform iterations: every lane still walking pops the same node -- the
+                // leading run of them (the shared descent) and all of them
+                bool lead = true;
+                for (size_t k = 0; k < maxlen; ++k) {
+                    int nd = -1;
+                    bool uni = true;
+                    for (int l = 0; l < 64 && uni; ++l) {
+                        if (k >= seq[l].size()) continue;
+                        if (nd < 0) nd = seq[l][k];
+                        else if (seq[l][k] != nd) uni = false;
+                    }
+                    lead = lead && uni;
+                    stats[15] += lead ? 1 : 0;
+                    stats[16] += uni ? 1 : 0;
+                }
+                stats[17] += 1;
+            }
+        }
+        return ORT_OK;
+    } catch (const std::exception& ex) {
+        return fail(nullptr, ORT_ERR_INTERNAL, ex.what());
+    }
+}
+
+
+// ANALYSIS-ONLY (tools/bounce_lines.py): the rays of bounce `bounce` (>= 1) of a tile's pixels,
+// 1 sample (the host restatement of the path: trace_ray + shade_bounce per bounce, as
+// shade_pixel), and per alive ray the loads of its bounce walk (the persistent kernel's walk,
+// rejected-sphere skip on): per step {node popped, first object entry of a leaf or -1, objects}.
+// rays: 8 floats per pixel {o.xyz, d.xyz, alive, steps}.  walks: 3 ints per step, ray after
+// ray; n_out[0] = steps written (all steps if <= cap).
+int ort_debug_bounce_walks(const float* cr, const float* ma, const float* fr, int32_t n_spheres,
+                           const float* node_min, const float* node_max, const int32_t* co, const int32_t* oo,
+                           const int32_t* cnt, int32_t n_nodes, const int32_t* idx, int64_t n_indices,
+                           const ort_params* p, const ort_tile* t, int32_t bounce, float* rays, int32_t* walks,
+                           int64_t cap, int64_t* n_out) {
+    try {
+        const std::string bad = check_params(p, t);
+        if (!bad.empty() || bounce < 1 || p->num_samples != 1) return fail(nullptr, ORT_ERR_INVALID_ARG, "bad args");
+        HostScene hs;
+        if (int rc = hs.build(cr, ma, fr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices, ORT_LAYOUT_COMPACT, 1, 0))
+            return fail(nullptr, rc, hs.error);
+        const ort::KScene& S = hs.S;
+        const ort::CompactLayout& cl = hs.cl;
+        const std::vector<float>&fplanes = hs.fplanes, &fplanes_b = hs.fplanes_b;
+        const std::vector<uint8_t>& lut = hs.lut;
+        const ort::PixelParams pp = pixel_params(p);
+        const TileMap tm = {t->x0, t->width, t->y0, t->rows, t->band_height, t->band_stride};
+        ort::LocalFrames lf;
+        ort::Counters cc;
+        for (int k = 0; k < 6; ++k) cc.v[k] = 0;
+        int64_t n = 0;
+        auto walk = [&](auto tag, const ort::Ray& ray, ort::V3 inv) -> int {
+            using Masks = decltype(tag);
+            ort::FastStateT<Masks> fs;
+            const float* pl = cl.depth > 8 ? fplanes_b.data() : fplanes.data();
+            if (!ort::fast_begin(S, pl, lut.data(), ray, inv, 0.001f, ORT_MAXFLOAT, fs)) return 0;
+            int steps = 0;
+            for (bool done = false; !done;) {
+                const uint2 rec = fs.rec;
+                const bool leaf = !(rec.y & ORT_INTERNAL_FLAG);
+                if (n < cap) {
+                    walks[3 * n] = fs.node;
+                    walks[3 * n + 1] = leaf ? (int)rec.x : -1;
+                    walks[3 * n + 2] = leaf ? (int)rec.y : 0;
+                }
+                ++n;
+                ++steps;
+                done = ort::fast_step<false>(S, lut.data(), fs, lf, cc);
+            }
+            return steps;
+        };
+        for (int row = 0; row < t->rows; ++row) {
+            const int y = tile_row_to_y(tm, row);
+            for (int c = 0; c < t->width; ++c) {
+                float* o = rays + 8 * ((size_t)row * t->width + c);
+                for (int k = 0; k < 8; ++k) o[k] = 0.0f;
+                if (y >= p->height) continue;
+                const int px = t->x0 + c;
+                ort_rng st;
+                ort::pixel_rng_init(pp, px, y, st);
+                ort::Ray ray = ort::primary_ray(pp, px, y, 0, st);
+                ort::V3 col = ort::mk(1.0f, 1.0f, 1.0f);
+                float importance = 1.0f;
+                bool alive = true;
+                for (int b = 0; b < bounce && alive; ++b) {
+                    if (importance < 0.01f) { alive = false; break; }
+                    float th;
+                    int entry;
+                    const int tr = ort::trace_ray<0, false>(S, fplanes.data(), lut.data(), ray, false, th, entry, lf, nullptr,
+                                                            nullptr, cc, b > 0, fplanes_b.data());
+                    ort::HitRec h;
+                    if (tr == ORT_TRACE_HIT) h = ort::hit_record<0>(S, ray, th, entry);
+                    if (ort::shade_bounce(tr == ORT_TRACE_HIT, h, ray, col, importance, st)) alive = false;
+                }
+                if (!alive || importance < 0.01f) continue;
+                ort::V3 inv = ort::mk(1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z);
+                o[0] = ray.o.x; o[1] = ray.o.y; o[2] = ray.o.z;
+                o[3] = ray.d.x; o[4] = ray.d.y; o[5] = ray.d.z;
+                o[6] = 1.0f;
+                if (!ort::fast_prepare(S, ray, inv)) { o[6] = 2.0f; continue; }  // deferred (exact walk)
+                o[7] = (float)(cl.depth > 8 ? walk(ort::Masks96Lean{}, ray, inv) : walk(ort::Masks64Plain{}, ray, inv));
+            }
+        }
+        *n_out = n;
+        return ORT_OK;
+    } catch (const std::exception& ex) {
+        return fail(nullptr, ORT_ERR_INTERNAL, ex.what());
+    }
+}
+
+int64_t ort_debug_walk_steps(const float* cr, const float* ma, const float* fr, int32_t n_spheres,
+                             const float* node_min, const float* node_max, const int32_t* co, const int32_t* oo,
+                             const int32_t* cnt, int32_t n_nodes, const int32_t* idx, int64_t n_indices,
+                             const ort_params* p, int32_t block_step, int32_t* lens, int64_t n_lens, uint16_t* steps,
+                             int64_t cap) {
+    try {
+        if (block_step < 1) return fail(nullptr, ORT_ERR_INVALID_ARG, "bad block_step");
+        HostScene hs;
+        if (int rc = hs.build(cr, ma, fr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices, ORT_LAYOUT_COMPACT, 1, 0))
+            return fail(nullptr, rc, hs.error);
+        if (hs.cl.depth > 8) return fail(nullptr, ORT_ERR_UNSUPPORTED, "walk_steps: depth <= 8 walk only");
+        const ort::KScene& S = hs.S;
+        const std::vector<float>& fplanes = hs.fplanes;
+        const std::vector<uint8_t>& lut = hs.lut;
+        const ort::PixelParams pp = pixel_params(p);
+        ort::LocalFrames lf;
+        const int bw = (p->width + 7) / 8, bh = (p->height + 7) / 8;
+        int64_t w = 0, n = 0;
+        for (int b = 0; b < bw * bh; b += block_step, ++w) {
+            const int bx = b % bw, by = b / bw;
+            for (int l = 0; l < 64; ++l) {
+                int32_t len = 0;
+                const int px = bx * 8 + (l & 7), py = by * 8 + (l >> 3);
+                if (px < p->width && py < p->height) {
+                    ort_rng st;
+                    ort::pixel_rng_init(pp, px, py, st);
+                    const ort::Ray ray = ort::primary_ray(pp, px, py, 0, st);
+                    const ort::V3 inv = ort::mk(1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z);
+                    ort::FastStateT<ort::Masks64> fs;
+                    if (ort::fast_path_ok(ray, inv, 0.001f, ORT_MAXFLOAT) &&
+                        ort::fast_begin(S, fplanes.data(), lut.data(), ray, inv, 0.001f, ORT_MAXFLOAT, fs)) {
+                        for (bool done = false; !done;) {
+                            ort::Counters cc;
+                            for (int k = 0; k < 6; ++k) cc.v[k] = 0;
+                            const uint32_t y = fs.rec.y;
+                            done = ort::fast_step<true>(S, lut.data(), fs, lf, cc);
+                            const uint64_t objs = cc.v[2] < 255 ? cc.v[2] : 255, kids = cc.v[0] - 1;
+                            const bool lk = (y & ORT_INTERNAL_FLAG) && (y & ORT_LEAFKIDS_FLAG);
+                            if (n < cap) steps[n] = (uint16_t)(objs | (kids < 15 ? kids : 15) << 8 | (lk ? 0x8000u : 0u));
+                            ++n;
+                            ++len;
+                        }
+                    }
+                }
+                if (64 * w + l < n_lens) lens[64 * w + l] = len;
+            }
+        }
+        return n <= cap ? n : -n;
+    } catch (const std::exception& ex) {
+        return fail(nullptr, ORT_ERR_INTERNAL, ex.what());
+    }
+}
+
+int ort_debug_lds_image(int32_t depth, const float* planes, uint32_t* image, int64_t cap_words, int32_t* layout) {
+    if (depth < 0 || depth > ORT_COMPACT_MAX_DEPTH || !planes || !layout)
+        return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_lds_image: bad argument");
+    const bool rev = ort::fast_rev_planes(depth);
+    const ort::LdsLayout l = ort::lds_layout(depth, rev);
+    layout[0] = l.frames;
+    layout[1] = l.lut;
+    layout[2] = 4 * ort::fast_plane_floats(depth, rev);
+    layout[3] = l.pop;
+    layout[4] = l.pop < 0 ? -1 : l.pop + ort::kPopTable2;
+    layout[5] = l.pop < 0 ? 0 : ort::kPopEntries;
+    layout[6] = ort::Masks64::kPopTable ? 1 : 0;
+    if (!image) return ORT_OK;
+    if (cap_words * 4 < (int64_t)l.frames) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_lds_image: image too small");
+    // what k_lds_image writes: the tables (fill_fast_planes), then the rank LUT
+    std::vector<float> img((size_t)l.frames / 4, 0.0f);
+    ort::fill_fast_planes(planes, img.data(), depth, rev);
+    uint8_t* lut = reinterpret_cast<uint8_t*>(img.data()) + l.lut;
+    for (int i = 0; i < (int)kRankLutBytes; ++i) lut[i] = ort::rank_lut_entry((uint32_t)i >> 8, (uint32_t)i & 255u);
+    std::memcpy(image, img.data(), (size_t)l.frames);
+    return ORT_OK;
+}
+
+int ort_debug_pop_coverage(uint64_t* hb_pops, uint64_t* sign_masks, int32_t reset) {
+    for (int i = 0; i < 64; ++i)
+        if (hb_pops) hb_pops[i] = ort::g_pop_cover[i];
+    for (int i = 0; i < 8; ++i)
+        if (sign_masks) sign_masks[i] = ort::g_pop_cover[64 + i];
+    if (reset)
+        for (int i = 0; i < 72; ++i) ort::g_pop_cover[i] = 0;
+    return ORT_OK;
+}
+
+}  // extern "C"

@@ -341,6 +341,20 @@ class Renderer:
         return Accumulation(self, params, tile or Tile.full(params))
 
     # -- ray queries ------------------------------------------------------------------
+    def _device_arg(self, who, x, what, dtype_name, need):
+        """The device address of x, a torch CUDA tensor on this device or a pointer (int)."""
+        if hasattr(x, "data_ptr"):
+            nbytes = x.numel() * x.element_size()
+            if str(x.dtype) != "torch." + dtype_name or not x.is_contiguous() or nbytes < need:
+                raise ValueError(f"{who}: {what} must be a contiguous {dtype_name} tensor of >= {need} bytes "
+                                 f"(got {x.dtype}, {nbytes} bytes, contiguous={x.is_contiguous()})")
+            if x.device.type != "cuda" or x.device.index != self.device:
+                raise ValueError(f"{who}: {what} is on {x.device}, the context traces on cuda:{self.device}")
+            return x.data_ptr()
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+            raise ValueError(f"{who}: {what} must be a torch CUDA tensor or a device pointer (int)")
+        return int(x)
+
     def trace_rays(self, rays, *, use_octree=True, sort=False, normals=False, out=None, stream=None, n=None,
                    mode="drawn", t_range=None):
         """What does each ray hit, and where (ort_trace_rays, include/ort.h): per ray the shader's
@@ -411,19 +425,6 @@ class Renderer:
             t, sph = np.ascontiguousarray(rec[:, 0]).view(np.float32), np.ascontiguousarray(rec[:, 1])
             return (t, sph, nrm) if normals else (t, sph)
 
-        def device_arg(x, what, dtype_name, need):  # a torch CUDA tensor on this device, or a pointer
-            if hasattr(x, "data_ptr"):
-                nbytes = x.numel() * x.element_size()
-                if str(x.dtype) != "torch." + dtype_name or not x.is_contiguous() or nbytes < need:
-                    raise ValueError(f"trace_rays: {what} must be a contiguous {dtype_name} tensor of >= {need} bytes "
-                                     f"(got {x.dtype}, {nbytes} bytes, contiguous={x.is_contiguous()})")
-                if x.device.type != "cuda" or x.device.index != self.device:
-                    raise ValueError(f"trace_rays: {what} is on {x.device}, the context traces on cuda:{self.device}")
-                return x.data_ptr()
-            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
-                raise ValueError(f"trace_rays: {what} must be a torch CUDA tensor or a device pointer (int)")
-            return int(x)
-
         if hasattr(rays, "data_ptr"):
             if rays.dim() != 2 or rays.shape[1] != 6:
                 raise ValueError(f"trace_rays: rays must have shape (n, 6) (got {tuple(rays.shape)})")
@@ -436,7 +437,7 @@ class Renderer:
             nr = int(n)
             if out is None or (isinstance(normals, (bool, np.bool_)) and normals):
                 raise ValueError("trace_rays: a device pointer needs out (and normals, where wanted) given")
-        q.rays, q.n_rays = C.c_void_p(device_arg(rays, "rays", "float32", 24 * nr)), nr
+        q.rays, q.n_rays = C.c_void_p(self._device_arg("trace_rays", rays, "rays", "float32", 24 * nr)), nr
         if out is None or (isinstance(normals, (bool, np.bool_)) and normals):
             import torch
             dev = torch.device("cuda", self.device)
@@ -445,12 +446,12 @@ class Renderer:
             if isinstance(normals, (bool, np.bool_)) and normals:
                 normals = torch.empty((nr, 3), dtype=torch.float32, device=dev)
         want_normals = not isinstance(normals, (bool, np.bool_))
-        q.hits = C.c_void_p(device_arg(out, "out", "int32", 8 * nr))
-        q.normals = C.c_void_p(device_arg(normals, "normals", "float32", 12 * nr)) if want_normals else None
+        q.hits = C.c_void_p(self._device_arg("trace_rays", out, "out", "int32", 8 * nr))
+        q.normals = C.c_void_p(self._device_arg("trace_rays", normals, "normals", "float32", 12 * nr)) if want_normals else None
         if t_range is not None:
             if hasattr(t_range, "data_ptr") and (t_range.dim() != 2 or tuple(t_range.shape) != (nr, 2)):
                 raise ValueError(f"trace_rays: t_range must have shape ({nr}, 2) (got {tuple(t_range.shape)})")
-            qx.t_range = C.c_void_p(device_arg(t_range, "t_range", "float32", 8 * nr))
+            qx.t_range = C.c_void_p(self._device_arg("trace_rays", t_range, "t_range", "float32", 8 * nr))
         q.on_device = 1
         self._check(trace())
         return (out, normals) if want_normals else out
@@ -541,19 +542,6 @@ class Renderer:
                    np.ascontiguousarray(rec[:, 1]).reshape(rows, width))
             return res + ((nrm,) if want_normals else ()) + ((ray,) if want_rays else ())
 
-        def device_arg(x, what, dtype_name, need):  # a torch CUDA tensor on this device, or a pointer
-            if hasattr(x, "data_ptr"):
-                nbytes = x.numel() * x.element_size()
-                if str(x.dtype) != "torch." + dtype_name or not x.is_contiguous() or nbytes < need:
-                    raise ValueError(f"trace_camera: {what} must be a contiguous {dtype_name} tensor of >= {need} bytes "
-                                     f"(got {x.dtype}, {nbytes} bytes, contiguous={x.is_contiguous()})")
-                if x.device.type != "cuda" or x.device.index != self.device:
-                    raise ValueError(f"trace_camera: {what} is on {x.device}, the context traces on cuda:{self.device}")
-                return x.data_ptr()
-            if not isinstance(x, (int, np.integer)):
-                raise ValueError(f"trace_camera: {what} must be a torch CUDA tensor or a device pointer (int)")
-            return int(x)
-
         def allocate(last, dtype_name):
             import torch
             return torch.empty((rows, width, last), dtype=getattr(torch, dtype_name), device=torch.device("cuda", self.device))
@@ -565,11 +553,11 @@ class Renderer:
         if is_flag(normals) and normals:
             normals = allocate(3, "float32")
         if hits:
-            q.hits = C.c_void_p(device_arg(out, "out", "int32", 8 * n))
+            q.hits = C.c_void_p(self._device_arg("trace_camera", out, "out", "int32", 8 * n))
         if want_normals:
-            q.normals = C.c_void_p(device_arg(normals, "normals", "float32", 12 * n))
+            q.normals = C.c_void_p(self._device_arg("trace_camera", normals, "normals", "float32", 12 * n))
         if want_rays:
-            q.rays = C.c_void_p(device_arg(rays, "rays", "float32", 24 * n))
+            q.rays = C.c_void_p(self._device_arg("trace_camera", rays, "rays", "float32", 24 * n))
         q.on_device = 1
         self._check(self._lib.ort_trace_camera(self._ctx, C.byref(p), C.byref(t), C.byref(q), s))
         res = ((out,) if hits else ()) + ((normals,) if want_normals else ()) + ((rays,) if want_rays else ())

@@ -211,6 +211,22 @@ def test_device_outputs_and_streams(renderers, full, name):
 
 
 @pytest.mark.parametrize("name", ["compact5", "compact10"])
+def test_more_pixels_than_the_resident_waves_take_singly(renderers, name):
+    """A 4096 x 2304 frame: more than 2^23 pixels, at least ORT_CHUNK_ADAPT (1024) per resident
+    wave on any grid, so the persistent loop draws its doubled chunks.  Device-resident; the
+    records equal trace_rays of the rays the call returned."""
+    import torch
+    w, h = 4096, 2304
+    d_rays = torch.empty((h, w, 6), dtype=torch.float32, device="cuda:0")
+    out, rays = renderers(name).trace_camera(cs.params(name, w, h, 1), rays=d_rays)
+    torch.cuda.synchronize()
+    assert rays is d_rays and out.shape == (h, w, 2)
+    again = renderers(name).trace_rays(d_rays.view(-1, 6))
+    torch.cuda.synchronize()
+    assert torch.equal(out.view(-1, 2), again)
+
+
+@pytest.mark.parametrize("name", ["compact5", "compact10"])
 def test_options_leave_the_records_alone(ort, full, name):
     """ORT_OPT_KID_SKIP 0 / 1 / 2, ORT_OPT_REFILL 1 / 16 / 64 and ORT_OPT_EXACT_TRAVERSAL: same records."""
     s, t, _ = ray_sets.scene(name)

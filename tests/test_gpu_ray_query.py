@@ -151,6 +151,27 @@ def test_sort_gives_the_same_records_in_the_same_order(renderers, full, name):
 
 
 @pytest.mark.parametrize("name", ["compact5", "compact10"])
+@pytest.mark.parametrize("sort", [False, True])
+def test_more_rays_than_the_resident_waves_take_singly(renderers, full, name, sort):
+    """2^23 + 1 rays: at least ORT_CHUNK_ADAPT (1024) items per resident wave on any grid (at most
+    6 waves/SIMD x 4 SIMDs x 256 CUs = 6144 waves), so the persistent loop draws its doubled
+    chunks.  The 3001-ray set tiled on the device; every record equals the tiled 3001-ray record."""
+    import torch
+    _, _, rays = ray_sets.scene(name)
+    n = (1 << 23) + 1
+    idx = torch.arange(n, device="cuda:0") % len(rays)
+    d_rays = torch.from_numpy(np.array(rays)).to("cuda:0")[idx].contiguous()
+    tt, sph, nrm = full(name)
+    want = torch.from_numpy(np.stack([bits(tt).view(np.int32), sph.astype(np.int32)], axis=1)).to("cuda:0")[idx]
+    want_nrm = torch.from_numpy(np.array(bits(nrm))).to("cuda:0")[idx]
+    out, got_nrm = renderers(name).trace_rays(d_rays, sort=sort, normals=True)
+    torch.cuda.synchronize()
+    assert out.shape == (n, 2) and got_nrm.shape == (n, 3)
+    assert torch.equal(out, want)
+    assert torch.equal(got_nrm.view(torch.int32), want_nrm)
+
+
+@pytest.mark.parametrize("name", ["compact5", "compact10"])
 def test_options_leave_the_records_alone(ort, full, name):
     """ORT_OPT_KID_SKIP 0 / 1 / 2, ORT_OPT_EXACT_TRAVERSAL 1 and ORT_OPT_REFILL: same records."""
     s, t, rays = ray_sets.scene(name)
