@@ -382,7 +382,8 @@ typedef struct ort_ray_query {
 } ort_ray_query;
 int ort_trace_rays(ort_ctx* ctx, const ort_ray_query* q, void* stream);
 
-/* Duration in milliseconds of the last ort_trace_rays' kernels (the sort's included, the host
+/* Duration in milliseconds of the last query's kernels -- ort_trace_rays, ort_trace_rays_ex,
+ * ort_trace_camera or ort_trace_radiance -- (the sort's included, the host
  * copies not), from HIP events on its stream.  Only valid once that stream has passed the query. */
 int ort_last_query_ms(ort_ctx* ctx, float* ms);
 
@@ -480,6 +481,65 @@ typedef struct ort_camera_query {
 } ort_camera_query;
 int ort_trace_camera(ort_ctx* ctx, const ort_params* params, const ort_tile* tile,
                      const ort_camera_query* q, void* stream);
+
+/* ---- radiance queries: what does this ray see? (light and irradiance probes, environment
+ * captures, fisheye / orthographic / stereo cameras, baking, re-shading a frame's pixels) --------
+ * ort_trace_radiance path-traces caller-supplied rays: per ray the mean of `paths` evaluations of
+ * the shader's radiance() (glsl:600-634), each drawing from the RNG state the one before left, in
+ * float32 with the shader's operations in the shader's order.  Per ray i:
+ *     st = states[i]; col = 0
+ *     repeat `paths` times:
+ *         ray = rays[i]; with ORT_RADIANCE_NORMALIZE direction = the shader's normalize(direction)
+ *         c = the body of radiance() after its normalize (glsl:603-633): at most max_depth bounces,
+ *             the `importance < 0.01` break, intersectScene(ray, 0.001, MAXFLOAT) by use_octree,
+ *             Material_bsdf drawing from st, the sky colour on a miss
+ *         col += c
+ *     radiance[i] = col / (float)paths            (paths == 1: col itself)
+ *     with ORT_RADIANCE_GAMMA: radiance[i] = pow(radiance[i], 1/2.2) per channel (glsl:659-661)
+ *     states_out[i] = st
+ * The paths of one ray are one sequential chain through st, exactly as a pixel's samples are;
+ * different rays are independent.  A 1-sample frame's pixel is this call with ORT_RADIANCE_GAMMA
+ * over the ray ort_trace_camera(ORT_CAMERA_FIRST_SAMPLE) returns and the pixel's seed advanced by
+ * the six draws that made that ray.
+ *   direction  used as given, as in ort_trace_rays, unless ORT_RADIANCE_NORMALIZE is set: the caller
+ *              passes unit directions.  A ray returned by ort_trace_camera is already the ray
+ *              radiance() walks: it must not be normalised again.
+ *   states     2 floats per ray: the shader's randState, each component in [0, 1).  A state with a
+ *              component outside [0, 1), NaN included, is not traced: its radiance is three zeros
+ *              and its states_out is the state as given (rand2D's float -> uint conversion is only
+ *              defined for states in that range).
+ *   states_out NULL, or 2 floats per ray; may be equal to states (it must not overlap it otherwise).
+ *   degenerate rays (zero, infinite or NaN components) terminate, as in ort_trace_rays, and get
+ *              whatever the shader's arithmetic gives for a miss.
+ * Shared with ort_trace_rays: on_device and the stream rules, the staging of host pointers through
+ * grow-only buffers the context owns, ort_last_query_ms, the buffers (order the queries of one
+ * context among themselves) and the isolation from render and accumulation state.  ORT_QUERY_SORT
+ * orders the first walk by the rays' coherence keys on the compact layout and is accepted and
+ * ignored on brute force; ORT_OPT_KID_SKIP, ORT_OPT_EXACT_TRAVERSAL and ORT_OPT_PIXEL_LDS_SCENE
+ * apply as in accumulation passes.  The records are the same under every value.  n_rays == 0:
+ * ORT_OK, nothing launched.  ORT_ERR_INVALID_ARG, before anything is launched and with the outputs
+ * untouched: NULL q, n_rays < 0 or > 2^30, NULL rays, states or radiance with n_rays > 0, pointers
+ * that are not 4-byte aligned, host states_out overlapping states without being equal to it,
+ * max_depth < 1, paths outside 1 .. 65536, unknown flag bits, reserved != 0.  ORT_ERR_UNSUPPORTED:
+ * use_octree = 1 on the explicit layout (the whole-pixel walk exists for the compact layout and
+ * brute force, as for ort_accum_begin).  ORT_ERR_NO_SCENE as ort_trace_rays.  Not in scope:
+ * queries on an ort_group, the explicit layout, a caller-chosen (t_min, t_max). */
+#define ORT_RADIANCE_NORMALIZE 2   /* apply radiance()'s normalize (glsl:602) to the direction first */
+#define ORT_RADIANCE_GAMMA     4   /* write pow(mean, 1/2.2) per channel (glsl:659-661) instead of the mean */
+typedef struct ort_radiance_query {          /* 64 bytes */
+    const ort_ray* rays;
+    int64_t n_rays;
+    const float* states;     /* 2 floats per ray: the shader's randState the ray's first path starts from */
+    float*       radiance;   /* 3 floats per ray */
+    float*       states_out; /* NULL, or 2 floats per ray: randState after the ray's last path; may be == states */
+    int32_t on_device;       /* != 0: all pointers are device pointers on ctx's device */
+    int32_t use_octree;      /* 1: the octree walk; 0: bruteForceIntersect */
+    int32_t max_depth;       /* >= 1: maxDepth of radiance() */
+    int32_t paths;           /* 1 .. 65536 paths per ray */
+    int32_t flags;           /* ORT_QUERY_SORT | ORT_RADIANCE_* */
+    int32_t reserved;        /* 0 */
+} ort_radiance_query;
+int ort_trace_radiance(ort_ctx* ctx, const ort_radiance_query* q, void* stream);
 
 /* ---- progressive frames: a frame's samples accumulated over several calls --------------------
  * The loop of an interactive caller (the reference's, src/main.cpp:120-163, with a camera driven

@@ -69,6 +69,7 @@ EXPORTED_SYMBOLS = (
     "ort_accum_free",
     "ort_trace_camera",
     "ort_trace_rays_ex",
+    "ort_trace_radiance",
 )
 ORT_GROUP_TRANSPORT_RCCL = 0
 ORT_GROUP_TRANSPORT_COPY = 1
@@ -91,6 +92,9 @@ QUERY_MODES = {"drawn": ORT_QUERY_DRAWN, "nearest": ORT_QUERY_NEAREST, "any": OR
 ORT_CAMERA_FIRST_SAMPLE = 0
 ORT_CAMERA_PIXEL_CENTRE = 1
 CAMERA_RAYS = {"first_sample": ORT_CAMERA_FIRST_SAMPLE, "pixel_centre": ORT_CAMERA_PIXEL_CENTRE}
+# ort_radiance_query.flags (ort_trace_radiance), beside ORT_QUERY_SORT
+ORT_RADIANCE_NORMALIZE = 2
+ORT_RADIANCE_GAMMA = 4
 
 
 class OrtParams(C.Structure):
@@ -138,6 +142,14 @@ class OrtCameraQuery(C.Structure):
     _fields_ = [
         ("rays", C.c_void_p), ("hits", C.c_void_p), ("normals", C.c_void_p),
         ("on_device", C.c_int32), ("which", C.c_int32), ("reserved", C.c_int32 * 2),
+    ]
+
+
+class OrtRadianceQuery(C.Structure):
+    _fields_ = [
+        ("rays", C.c_void_p), ("n_rays", C.c_int64), ("states", C.c_void_p), ("radiance", C.c_void_p),
+        ("states_out", C.c_void_p), ("on_device", C.c_int32), ("use_octree", C.c_int32), ("max_depth", C.c_int32),
+        ("paths", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
     ]
 
 
@@ -189,6 +201,7 @@ def _declare(lib, debug: str = "none"):
         "ort_last_query_ms": (C.c_int, [_vp, _fp]),
         "ort_trace_rays_ex": (C.c_int, [_vp, C.POINTER(OrtRayQueryEx), _vp]),
         "ort_trace_camera": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(OrtCameraQuery), _vp]),
+        "ort_trace_radiance": (C.c_int, [_vp, C.POINTER(OrtRadianceQuery), _vp]),
         "ort_accum_begin": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(_vp)]),
         "ort_accum_render": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(OrtOutput), _vp]),
         "ort_accum_restart": (C.c_int, [_vp, _vp, C.POINTER(OrtParams)]),
@@ -241,6 +254,9 @@ def _declare(lib, debug: str = "none"):
                                               C.c_int32, _fp, C.c_int64, C.c_int32, _fp, _vp, _fp]),
         "ort_debug_camera_query": (C.c_int, [_fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip, C.c_int64, C.c_int32,
                                              C.POINTER(OrtParams), C.POINTER(OrtTile), C.c_int32, _fp, _vp, _fp]),
+        "ort_debug_radiance_rays": (C.c_int, [_fp, _fp, _fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip, C.c_int64,
+                                              C.c_int32, C.c_int32, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                              _fp, _fp]),
         "ort_debug_split_rays": (C.c_int, [_fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip, C.c_int64, _fp,
                                            C.c_int32, C.c_int32, C.c_int32, _ip]),
         "ort_debug_emulate_render": (C.c_int, [_fp, _fp, _fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip,
@@ -253,8 +269,8 @@ def _declare(lib, debug: str = "none"):
     for name, (res, args) in sig.items():
         if name.startswith("ort_debug_") and (debug == "none" or (debug == "present" and not hasattr(lib, name))):
             continue
-        if name in ("ort_trace_camera", "ort_trace_rays_ex") and debug == "present" and not hasattr(lib, name):
-            continue  # an ORT_LIB override of a build from before camera queries / query modes (A/B runs): calling it raises
+        if name in ("ort_trace_camera", "ort_trace_rays_ex", "ort_trace_radiance") and debug == "present" and not hasattr(lib, name):
+            continue  # an ORT_LIB override of a build from before these queries (A/B runs): calling it raises
         f = getattr(lib, name)
         f.restype = res
         f.argtypes = args

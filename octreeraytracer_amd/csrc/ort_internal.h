@@ -91,6 +91,19 @@ int ort_debug_camera_query(const float* sphere_center_radius, int32_t n_spheres,
                            const int32_t* object_count, int32_t n_nodes, const int32_t* object_indices, int64_t n_indices,
                            int32_t layout, const ort_params* params, const ort_tile* tile, int32_t which, float* rays,
                            ort_ray_hit* hits, float* normals);
+// TEST-ONLY: ort_trace_radiance on the host CPU: per ray the chain of `paths` paths from its state,
+// the kernels' own per-bounce functions (render_core.h trace_ray, hit_record, shade_bounce) in
+// shade_pixel's order -- layout ORT_LAYOUT_COMPACT with use_octree 1, brute force with use_octree 0
+// (the explicit layout with use_octree 1: ORT_ERR_UNSUPPORTED, as the entry point).  flags:
+// ORT_RADIANCE_* (ORT_QUERY_SORT is accepted and changes nothing).  radiance: 3 floats per ray;
+// states_out: NULL or 2 floats per ray, may be == states.
+int ort_debug_radiance_rays(const float* sphere_center_radius, const float* sphere_mat_albedo,
+                            const float* sphere_fuzz_ri, int32_t n_spheres, const float* node_min,
+                            const float* node_max, const int32_t* children_offset, const int32_t* objects_offset,
+                            const int32_t* object_count, int32_t n_nodes, const int32_t* object_indices,
+                            int64_t n_indices, int32_t layout, int32_t use_octree, const float* rays,
+                            const float* states, int64_t n_rays, int32_t max_depth, int32_t paths, int32_t flags,
+                            float* radiance, float* states_out);
 // ANALYSIS-ONLY: lane overlap of sampled 8x8 primary-ray blocks (tools/wave_stats.py).
 int ort_debug_wave_stats(const float* sphere_center_radius, const float* sphere_mat_albedo,
                          const float* sphere_fuzz_ri, int32_t n_spheres, const float* node_min,

@@ -1892,10 +1892,10 @@ struct DevBuf {
 
 // The queries' own state (ort_trace_rays, ort_trace_rays_ex, ort_trace_camera: ray_query.inc), none of
 // the per-frame pipeline's: the staging of host arrays (grow-only; trange: ort_trace_rays_ex's
-// intervals), the defer list and the {deferred count, cursor} counters, ORT_QUERY_SORT's keys and
+// intervals; states, radiance: ort_trace_radiance's), the defer list and the {deferred count, cursor} counters, ORT_QUERY_SORT's keys and
 // lists, the timing events of the last query.
 struct QueryState {
-    DevBuf rays, hits, normals, trange;
+    DevBuf rays, hits, normals, trange, states, radiance;
     DevBuf defer, sync;
     DevBuf keys, keys2, vals, list, temp;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -2103,7 +2103,7 @@ void free_buf(DevBuf& b) {
 }
 
 void free_query(QueryState& q) {
-    for (DevBuf* b : {&q.rays, &q.hits, &q.normals, &q.trange, &q.defer, &q.sync, &q.keys, &q.keys2, &q.vals, &q.list, &q.temp})
+    for (DevBuf* b : {&q.rays, &q.hits, &q.normals, &q.trange, &q.states, &q.radiance, &q.defer, &q.sync, &q.keys, &q.keys2, &q.vals, &q.list, &q.temp})
         free_buf(*b);
     if (q.ev0) (void)hipEventDestroy(q.ev0);
     if (q.ev1) (void)hipEventDestroy(q.ev1);
@@ -3697,3 +3697,5 @@ int ort_count_traffic(ort_ctx* ctx, const ort_params* params, const ort_tile* ti
 #include "camera_query.inc"
 // Query modes (ort_trace_rays_ex, ort_debug_query_rays_ex): last, so that every earlier kernel keeps its place.
 #include "ray_modes.inc"
+// Radiance queries (ort_trace_radiance, ort_debug_radiance_rays): last, so that every earlier kernel keeps its place.
+#include "radiance_query.inc"

@@ -204,6 +204,19 @@ int Raytracer::traceCamera(const Camera& cam, const ort_tile& tile, const ort_ca
     return ort_trace_camera(ctx, &p, &tile, &query, nullptr);
 }
 
+int Raytracer::traceRadiance(const ort_ray* rays, const float* states, int64_t n, int maxDepth, int paths, float* radiance,
+                             float* statesOut, int flags) {
+    if (!ctx && !group && !initialize()) return ORT_ERR_HIP;
+    if (group) return ORT_ERR_UNSUPPORTED;  // queries run on one context
+    if (!sceneReady) {
+        setupScene();
+        setupBuffers();
+        if (!sceneReady) return ORT_ERR_INVALID_ARG;
+    }
+    const ort_radiance_query q = {rays, n, states, radiance, statesOut, 0, cfg.useOctree, maxDepth, paths, flags, 0};
+    return ort_trace_radiance(ctx, &q, nullptr);
+}
+
 int Raytracer::pick(const Camera& cam, int x, int y, ort_ray_hit* hit, float point[3]) {
     ort_ray ray;
     ort_ray_hit h = {0.0f, -1};

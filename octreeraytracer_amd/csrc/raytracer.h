@@ -105,6 +105,15 @@ public:
     // builds and uploads the scene on first use.  Single-device configurations only (a group:
     // ORT_ERR_UNSUPPORTED).
     int traceCamera(const Camera& cam, const ort_tile& tile, const ort_camera_query& query);
+    // Radiance queries (include/ort.h ort_trace_radiance): what each of n rays sees in the current
+    // scene -- radiance[3 i ..] the mean of `paths` paths of at most maxDepth bounces along ray i,
+    // chained through the RNG state states[2 i ..] (each component in [0, 1)) as a pixel's samples
+    // are; statesOut (nullptr, or 2 floats per ray, may be == states) the states the chains end
+    // with; flags ORT_QUERY_SORT | ORT_RADIANCE_*.  Directions are used as given (unit, or
+    // ORT_RADIANCE_NORMALIZE).  By the walk the frames are drawn with (cfg.useOctree).  Host
+    // pointers, synchronous; single-device configurations only (a group: ORT_ERR_UNSUPPORTED).
+    int traceRadiance(const ort_ray* rays, const float* states, int64_t n, int maxDepth, int paths, float* radiance,
+                      float* statesOut = nullptr, int flags = 0);
     // The sphere under pixel (x, y) of cam's frame, by the pinhole ray through the pixel centre
     // (ORT_CAMERA_PIXEL_CENTRE): *hit = {t, sphere index in getSpheres()} ({0, -1}: nothing
     // there), point (may be nullptr) = origin + t * direction.  y is a GL row, 0 at the bottom:

@@ -575,8 +575,95 @@ class Renderer:
         point = (o + (t[0, 0] * d).astype(np.float32)).astype(np.float32)
         return int(sphere[0, 0]), float(t[0, 0]), point
 
+    def trace_radiance(self, rays, states, *, max_depth, paths=1, use_octree=True, sort=False, normalize=False,
+                       gamma=False, states_out=False, out=None, stream=None, n=None):
+        """What each ray sees (ort_trace_radiance, include/ort.h): per ray the mean of `paths`
+        evaluations of the shader's radiance() of at most max_depth bounces, chained through the
+        ray's RNG state as a pixel's samples are -- bit for bit what the frames are made of.
+
+        rays: (n, 6) float32 (origin, direction; unit directions, or normalize=True for the
+        shader's normalize).  states: (n, 2) float32, each component in [0, 1) (``rng_states``); a
+        ray whose state is not gets zeros and its state back.  gamma: pow(mean, 1/2.2) as the last
+        lines of the shader's main().  sort: walk the rays in coherence order (same records).
+        Host (numpy arrays): returns the (n, 3) float32 radiance -- out may be a C-contiguous
+        float32 array of >= 3 n elements to receive it -- and with states_out=True also the (n, 2)
+        end states; states_out may be an (n, 2) float32 array, `states` itself included.
+        Device (torch CUDA tensors on this device, or device pointers with n): everything stays on
+        the device; returns out, an (n, 3) float32 tensor (allocated when None; pointers need out
+        given), and with states_out (True allocates it; a tensor -- `states` itself is allowed --
+        or a pointer is used) the end states.  stream: as render()."""
+        who = "trace_radiance"
+        max_depth, paths = int(max_depth), int(paths)  # (their ranges: the ABI's refusal)
+        flags = ((L.ORT_QUERY_SORT if sort else 0) | (L.ORT_RADIANCE_NORMALIZE if normalize else 0) |
+                 (L.ORT_RADIANCE_GAMMA if gamma else 0))
+        s = C.c_void_p(int(stream)) if stream else None
+        q = L.OrtRadianceQuery(None, 0, None, None, None, 0, 1 if use_octree else 0, max_depth, paths, flags, 0)
+        is_flag = lambda x: isinstance(x, (bool, np.bool_))  # noqa: E731
+        want_states = not is_flag(states_out) or bool(states_out)
+
+        def host_array(x, what, cols, nr):
+            if (not isinstance(x, np.ndarray) or x.dtype != np.float32 or x.ndim != 2 or x.shape != (nr, cols) or
+                    not x.flags.c_contiguous):
+                raise ValueError(f"{who}: {what} must be a C-contiguous ({nr}, {cols}) float32 array "
+                                 f"(got {getattr(x, 'dtype', type(x))}, shape {getattr(x, 'shape', None)})")
+            return x
+
+        if isinstance(rays, np.ndarray):
+            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 6 or not rays.flags.c_contiguous:
+                raise ValueError(f"{who}: rays must be a C-contiguous (n, 6) float32 array (got {rays.dtype}, "
+                                 f"shape {rays.shape}, contiguous={rays.flags.c_contiguous})")
+            nr = rays.shape[0]
+            if n is not None and int(n) != nr:
+                raise ValueError(f"{who}: n = {n} but rays holds {nr}")
+            host_array(states, "with host rays, states", 2, nr)
+            if out is None:
+                out = np.empty((nr, 3), np.float32)
+            if (not isinstance(out, np.ndarray) or out.dtype != np.float32 or not out.flags.c_contiguous or
+                    out.nbytes < 12 * nr):
+                raise ValueError(f"{who}: out must be a C-contiguous float32 numpy array of >= {12 * nr} bytes")
+            if is_flag(states_out):
+                states_out = np.empty((nr, 2), np.float32) if states_out else None
+            else:
+                host_array(states_out, "with host rays, states_out", 2, nr)
+            q.rays, q.n_rays = rays.ctypes.data_as(C.c_void_p), nr
+            q.states = states.ctypes.data_as(C.c_void_p)
+            q.radiance = out.ctypes.data_as(C.c_void_p)
+            q.states_out = states_out.ctypes.data_as(C.c_void_p) if want_states else None
+            self._check(self._lib.ort_trace_radiance(self._ctx, C.byref(q), s))
+            rad = out.reshape(-1)[:3 * nr].reshape(nr, 3)
+            return (rad, states_out) if want_states else rad
+
+        if hasattr(rays, "data_ptr"):
+            if rays.dim() != 2 or rays.shape[1] != 6:
+                raise ValueError(f"{who}: rays must have shape (n, 6) (got {tuple(rays.shape)})")
+            nr = rays.shape[0]
+            if n is not None and int(n) != nr:
+                raise ValueError(f"{who}: n = {n} but rays holds {nr}")
+        else:
+            if n is None or int(n) < 0:
+                raise ValueError(f"{who}: a device pointer needs n, the number of rays")
+            nr = int(n)
+            if out is None or (is_flag(states_out) and states_out):
+                raise ValueError(f"{who}: a device pointer needs out (and states_out, where wanted) given")
+        if hasattr(states, "data_ptr") and (states.dim() != 2 or tuple(states.shape) != (nr, 2)):
+            raise ValueError(f"{who}: states must have shape ({nr}, 2) (got {tuple(states.shape)})")
+        q.rays, q.n_rays = C.c_void_p(self._device_arg(who, rays, "rays", "float32", 24 * nr)), nr
+        q.states = C.c_void_p(self._device_arg(who, states, "states", "float32", 8 * nr))
+        if out is None or (is_flag(states_out) and states_out):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if out is None:
+                out = torch.empty((nr, 3), dtype=torch.float32, device=dev)
+            if is_flag(states_out) and states_out:
+                states_out = torch.empty((nr, 2), dtype=torch.float32, device=dev)
+        q.radiance = C.c_void_p(self._device_arg(who, out, "out", "float32", 12 * nr))
+        q.states_out = C.c_void_p(self._device_arg(who, states_out, "states_out", "float32", 8 * nr)) if want_states else None
+        q.on_device = 1
+        self._check(self._lib.ort_trace_radiance(self._ctx, C.byref(q), s))
+        return (out, states_out) if want_states else out
+
     def last_query_ms(self) -> float:
-        """The last trace_rays' or trace_camera's kernels (a sort included), from HIP events on its stream."""
+        """The last trace_rays', trace_camera's or trace_radiance's kernels (a sort included), from HIP events on its stream."""
         ms = C.c_float()
         self._check(self._lib.ort_last_query_ms(self._ctx, C.byref(ms)))
         return ms.value
@@ -812,3 +899,50 @@ def camera_query_host(spheres: SphereSet | None, tree: FlatOctree | None, params
     tt = np.ascontiguousarray(rec[:, 0]).view(np.float32).reshape(rows, width)
     sph = np.ascontiguousarray(rec[:, 1]).reshape(rows, width)
     return (rays, tt, sph, nrm) if normals else (rays, tt, sph)
+
+
+def rng_states(n: int, seed: int = 0) -> np.ndarray:
+    """(n, 2) float32 RNG states for ``Renderer.trace_radiance``, each component in [0, 1), from
+    np.random.default_rng(seed): one independent chain per ray."""
+    return np.random.default_rng(seed).random((int(n), 2), dtype=np.float32)
+
+
+def radiance_rays_host(spheres: SphereSet, tree: FlatOctree | None, rays, states, *, max_depth: int, paths: int = 1,
+                       layout: int = L.ORT_LAYOUT_COMPACT, use_octree: bool = True, sort: bool = False,
+                       normalize: bool = False, gamma: bool = False, states_out=False):
+    """TEST-ONLY: ``Renderer.trace_radiance`` on the host CPU (ort_debug_radiance_rays: the kernels'
+    own per-bounce functions, one ray's chain after another).  Returns the (n, 3) radiance, and with
+    states_out (True, or an (n, 2) float32 array to receive them, `states` itself allowed) the end states."""
+    lib = L.analysis_lib()
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    n = rays.shape[0]
+    states = np.ascontiguousarray(states, np.float32)
+    if states.shape != (n, 2):
+        raise ValueError(f"radiance_rays_host: states must have shape ({n}, 2) (got {states.shape})")
+    if isinstance(states_out, (bool, np.bool_)):
+        st_out = np.empty((n, 2), np.float32) if states_out else None
+    else:
+        st_out = states_out
+        if (not isinstance(st_out, np.ndarray) or st_out.dtype != np.float32 or st_out.shape != (n, 2) or
+                not st_out.flags.c_contiguous):
+            raise ValueError(f"radiance_rays_host: states_out must be a C-contiguous ({n}, 2) float32 array")
+    flags = ((L.ORT_QUERY_SORT if sort else 0) | (L.ORT_RADIANCE_NORMALIZE if normalize else 0) |
+             (L.ORT_RADIANCE_GAMMA if gamma else 0))
+    cr = np.ascontiguousarray(spheres.center_radius, np.float32)
+    ma = np.ascontiguousarray(spheres.mat_albedo, np.float32)
+    fr = np.ascontiguousarray(spheres.fuzz_ri, np.float32)
+    if tree is None:
+        keep = ()
+        args = (None, None, None, None, None, 0, None, 0)
+    else:
+        keep = tuple(np.ascontiguousarray(a, t) for a, t in (
+            (tree.node_min, np.float32), (tree.node_max, np.float32), (tree.children_offset, np.int32),
+            (tree.objects_offset, np.int32), (tree.object_count, np.int32), (tree.object_indices, np.int32)))
+        args = (L.fptr(keep[0]), L.fptr(keep[1]), L.iptr(keep[2]), L.iptr(keep[3]), L.iptr(keep[4]),
+                tree.n_nodes, L.iptr(keep[5]), tree.n_indices)
+    rad = np.empty((n, 3), np.float32)
+    L.acheck(lib.ort_debug_radiance_rays(L.fptr(cr), L.fptr(ma), L.fptr(fr), spheres.n, *args, int(layout),
+                                        1 if use_octree else 0, L.fptr(rays), L.fptr(states), n, int(max_depth), int(paths),
+                                        flags, L.fptr(rad), L.fptr(st_out)))
+    del keep
+    return (rad, st_out) if st_out is not None else rad
