@@ -22,6 +22,7 @@ struct HostScene {
     ort::CompactLayout cl;
     std::vector<float> fplanes, fplanes_b;
     std::vector<uint8_t> lut;           // the rank LUT
+    std::vector<uint4> leaf16;          // depth <= 8: KScene::leaf16, as k_leaf16 derives it
     const uint8_t* rank_lut = nullptr;  // ... null for an unordered tree (and without the compact layout)
     std::string error;                  // of a failed build
     HostScene() { std::memset(&S, 0, sizeof(S)); }
@@ -67,6 +68,12 @@ struct HostScene {
             S.leaf_idx = cl.leaf_idx.data();
             S.planes = cl.planes.data();
             S.depth = cl.depth;
+            if (ort::Masks64::kLeafInline && cl.depth <= 8) {
+                fill_leaf16((const uint2*)cl.node.data(), (int64_t)(cl.node.size() / 2), (const uint4*)cl.leaf_sph.data(),
+                            (int64_t)(cl.leaf_sph.size() / 4), leaf16);
+                S.leaf16 = leaf16.data();
+                S.leaf16_bytes = (uint32_t)(16 * leaf16.size());
+            }
             fplanes.resize(ort::fast_plane_floats(cl.depth));
             ort::fill_fast_planes(cl.planes.data(), fplanes.data(), cl.depth);
             const bool rev_b = ort::Masks96Lean::kRevPlanes || ort::fast_rev_planes(cl.depth);
@@ -91,6 +98,17 @@ struct HostScene {
         S.count = cnt;
         S.indices = idx;
         return ORT_OK;
+    }
+
+    // k_leaf16 on the host: the same ort::leaf16_record per node
+    static void fill_leaf16(const uint2* node, int64_t n, const uint4* leaf_sph, int64_t n_ent, std::vector<uint4>& out) {
+        out.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+            const uint2 rec = node[i];
+            uint4 sp = make_uint4(0u, 0u, 0u, ort::kLeaf16ListTag);
+            if (rec.y == 1u && (int64_t)rec.x < n_ent) sp = leaf_sph[rec.x];
+            out[(size_t)i] = ort::leaf16_record(rec, sp);
+        }
     }
 
 private:
@@ -573,6 +591,54 @@ int ort_debug_lds_image(int32_t depth, const float* planes, uint32_t* image, int
     uint8_t* lut = reinterpret_cast<uint8_t*>(img.data()) + l.lut;
     for (int i = 0; i < (int)kRankLutBytes; ++i) lut[i] = ort::rank_lut_entry((uint32_t)i >> 8, (uint32_t)i & 255u);
     std::memcpy(image, img.data(), (size_t)l.frames);
+    return ORT_OK;
+}
+
+// tests/test_leaf_inline.py: the compact layout's node[] (2 words a node), leaf_sph[] (4 words an
+// entry) and the leaf16 records derived from them (4 words a node; none when the build has no
+// Masks64::kLeafInline or the tree is deeper than 8), each into its array when given; sizes[3] =
+// {nodes, entries, leaf16 records}.
+int ort_debug_leaf16(const float* cr, int32_t n_spheres, const float* node_min, const float* node_max, const int32_t* co,
+                     const int32_t* oo, const int32_t* cnt, int32_t n_nodes, const int32_t* idx, int64_t n_indices,
+                     uint32_t* node, uint32_t* leaf_sph, uint32_t* leaf16, int64_t* sizes) {
+    try {
+        if (!sizes) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_leaf16: null sizes");
+        HostScene hs;
+        if (int rc = hs.build(cr, nullptr, nullptr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices,
+                              ORT_LAYOUT_COMPACT, 1, HostScene::kValidate))
+            return fail(nullptr, rc, hs.error);
+        sizes[0] = (int64_t)(hs.cl.node.size() / 2);
+        sizes[1] = (int64_t)(hs.cl.leaf_sph.size() / 4);
+        sizes[2] = (int64_t)hs.leaf16.size();
+        if (node) std::memcpy(node, hs.cl.node.data(), 4 * hs.cl.node.size());
+        if (leaf_sph) std::memcpy(leaf_sph, hs.cl.leaf_sph.data(), 4 * hs.cl.leaf_sph.size());
+        if (leaf16 && !hs.leaf16.empty()) std::memcpy(leaf16, hs.leaf16.data(), 16 * hs.leaf16.size());
+        return ORT_OK;
+    } catch (const std::exception& ex) {
+        return fail(nullptr, ORT_ERR_INTERNAL, ex.what());
+    }
+}
+
+// tests/test_gpu_leaf_inline.py: a context's device leaf16 records copied to out (cap records);
+// returns their number through n.
+int ort_debug_ctx_leaf16(ort_ctx* ctx, uint32_t* out, int64_t cap, int64_t* n) {
+    if (!ctx || !n) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_debug_ctx_leaf16: null argument");
+    *n = ctx->leaf16.p ? (int64_t)(ctx->leaf16.bytes / 16) : 0;
+    if (!out || *n == 0) return ORT_OK;
+    if (cap < *n) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_debug_ctx_leaf16: out too small");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(out, ctx->leaf16.p, ctx->leaf16.bytes, hipMemcpyDeviceToHost));
+    return ORT_OK;
+}
+
+// The kLeafInline host walk's sphere tests and accepted hits per record form (render_core.h
+// g_leaf_forms): {inline tests, inline hits, list tests, list hits}.
+int ort_debug_leaf_forms(uint64_t* out4, int32_t reset) {
+    for (int i = 0; i < 4; ++i) {
+        if (out4) out4[i] = ort::g_leaf_forms[i];
+        if (reset) ort::g_leaf_forms[i] = 0;
+    }
     return ORT_OK;
 }
 

@@ -139,4 +139,18 @@ int ort_debug_lds_image(int32_t depth, const float* planes, uint32_t* image, int
 // mask bit hb = 8 L + 7 - rank (hb_pops[64]) and under which direction-sign mask m
 // (sign_masks[8], counted per pop) since the last reset; reset != 0 clears the counts.
 int ort_debug_pop_coverage(uint64_t* hb_pops, uint64_t* sign_masks, int32_t reset);
+// TEST-ONLY: the compact layout of a tree as the host emulation walks it: node[] (2 words a node),
+// leaf_sph[] (4 words an entry) and the 16-byte leaf records derived from them (render_core.h
+// leaf16_record; 4 words a node, none for a tree deeper than 8 or a build without
+// Masks64::kLeafInline), each copied when its pointer is given.  sizes[3] = {nodes, entries,
+// leaf records}: call once with null arrays for the sizes.
+int ort_debug_leaf16(const float* sphere_center_radius, int32_t n_spheres, const float* node_min, const float* node_max,
+                     const int32_t* children_offset, const int32_t* objects_offset, const int32_t* object_count,
+                     int32_t n_nodes, const int32_t* object_indices, int64_t n_indices, uint32_t* node,
+                     uint32_t* leaf_sph, uint32_t* leaf16, int64_t* sizes);
+// TEST-ONLY: a context's device leaf records (k_leaf16) copied to out[4 cap]; *n = their number.
+int ort_debug_ctx_leaf16(ort_ctx* ctx, uint32_t* out, int64_t cap, int64_t* n);
+// TEST-ONLY: sphere tests and accepted hits of the host's depth <= 8 camera walks per leaf record
+// form since the last reset: {inline tests, inline hits, list tests, list hits}.
+int ort_debug_leaf_forms(uint64_t* out4, int32_t reset);
 }

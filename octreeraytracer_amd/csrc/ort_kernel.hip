@@ -2036,6 +2036,7 @@ struct ort_ctx {
     DevBuf sph_cr, sph_ma, sph_fr;
     DevBuf node, leaf_sph, leaf_idx, planes, kid;  // compact
     DevBuf nk;                                   // ... node records and kid entries interleaved (build_nk)
+    DevBuf leaf16;                               // ... depth <= 8: the 16-byte leaf records (build_leaf16)
     DevBuf lds_img;                              // compact: the workgroup LDS image (k_lds_image)
     DevBuf lds_rev;                              // ... depth 9-10: the reversed-table image (persistent kernel)
     DevBuf nodeA, nodeB, cnt, indices;           // explicit
@@ -2114,7 +2115,7 @@ void free_query(QueryState& q) {
 // ort_scene_get_info sums.
 template <class C, class F>
 void each_scene_buffer(C& c, F f) {
-    for (auto* b : {&c.sph_cr, &c.sph_ma, &c.sph_fr, &c.node, &c.kid, &c.nk, &c.leaf_sph, &c.leaf_idx, &c.planes,
+    for (auto* b : {&c.sph_cr, &c.sph_ma, &c.sph_fr, &c.node, &c.kid, &c.nk, &c.leaf16, &c.leaf_sph, &c.leaf_idx, &c.planes,
                     &c.lds_img, &c.lds_rev, &c.nodeA, &c.nodeB, &c.cnt, &c.indices})
         f(*b);
 }
@@ -2179,6 +2180,32 @@ int build_nk(ort_ctx* ctx) {
     if ((rc = upload(ctx, ctx->nk, nullptr, 16 * (size_t)n))) return rc;
     hipLaunchKernelGGL(k_interleave_nk, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
                        (const uint2*)ctx->node.p, (const uint2*)ctx->kid.p, (uint4*)ctx->nk.p, n);
+    HIPCHK(ctx, hipGetLastError());
+    return ORT_OK;
+}
+
+// KScene::leaf16 from node[] and leaf_sph[] (n_ent entries), record by record through
+// ort::leaf16_record -- the function the host emulation fills its own array with.
+__global__ void __launch_bounds__(kBlock) k_leaf16(const uint2* node, const uint4* leaf_sph, int64_t n_ent, uint4* leaf16, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint2 rec = node[i];
+    uint4 sp = make_uint4(0u, 0u, 0u, ort::kLeaf16ListTag);  // (an offset outside leaf_sph[]: the list form)
+    if (rec.y == 1u && (int64_t)rec.x < n_ent) sp = leaf_sph[rec.x];
+    leaf16[i] = ort::leaf16_record(rec, sp);
+}
+
+// The depth <= 8 camera walk reads its leaf children's records from leaf16 (Masks64::kLeafInline):
+// one per node id, 16 bytes, so at most 307 MB (a full depth-8 tree).
+int build_leaf16(ort_ctx* ctx) {
+    free_buf(ctx->leaf16);
+    const int64_t n = (int64_t)(ctx->node.bytes / 8);
+    if (!ort::Masks64::kLeafInline || ctx->depth > 8 || n == 0) return ORT_OK;
+    int rc;
+    if ((rc = upload(ctx, ctx->leaf16, nullptr, 16 * (size_t)n))) return rc;
+    hipLaunchKernelGGL(k_leaf16, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
+                       (const uint2*)ctx->node.p, (const uint4*)ctx->leaf_sph.p, (int64_t)(ctx->leaf_sph.bytes / 16),
+                       (uint4*)ctx->leaf16.p, n);
     HIPCHK(ctx, hipGetLastError());
     return ORT_OK;
 }
@@ -2258,7 +2285,7 @@ int build_impl(ort_ctx* ctx, const float* cr, const float* ma, const float* fr, 
         ctx->leaf_sph = {cd.leaf_sph, cd.leaf_bytes};
         ctx->leaf_idx = {cd.leaf_idx, cd.idx_bytes};
         ctx->planes = {cd.planes, cd.plane_bytes};
-        if ((rc = build_lds_image(ctx)) || (rc = build_nk(ctx))) {
+        if ((rc = build_lds_image(ctx)) || (rc = build_nk(ctx)) || (rc = build_leaf16(ctx))) {
             ort::freeGpuTree(t);
             return rc;
         }
@@ -2317,6 +2344,7 @@ int upload_impl(ort_ctx* ctx, const ort::SceneInput& in) {
             if ((rc = upload(ctx, ctx->planes, cl.planes.data(), 4 * cl.planes.size()))) return rc;
             if ((rc = build_lds_image(ctx))) return rc;
             if ((rc = build_nk(ctx))) return rc;
+            if ((rc = build_leaf16(ctx))) return rc;
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         } else {
             const int d = ort::treeDepth(in);
@@ -2356,6 +2384,8 @@ ort::KScene device_scene(const ort_ctx* c) {
     S.nk = c->kid_skip == 1 ? (const uint4*)c->nk.p : nullptr;  // 2: the separate arrays (testing)
     S.nk_bytes = (uint32_t)c->nk.bytes;
     S.tail_base = (uint32_t)c->n_indices;
+    S.leaf16 = (const uint4*)c->leaf16.p;
+    S.leaf16_bytes = (uint32_t)c->leaf16.bytes;
     S.leaf_sph = (const float4*)c->leaf_sph.p;
     S.node_bytes = (uint32_t)c->node.bytes;
     S.leaf_bytes = (uint32_t)c->leaf_sph.bytes;

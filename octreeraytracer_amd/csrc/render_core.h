@@ -108,6 +108,8 @@ struct KScene {
     const uint4* nk;         // per node: {record, kid entry} interleaved (one 16-byte load), or null
     uint32_t nk_bytes;
     uint32_t tail_base;      // = n_indices: a one-sphere leaf's objectsOffset is tail_base + sphere
+    const uint4* leaf16;     // depth <= 8: per node id the 16-byte leaf record (leaf16_record), or null
+    uint32_t leaf16_bytes;
     // walks with Masks::kLdsScene (ort_pixel_paths on small scenes): LDS byte addresses of
     // workgroup copies of nk[] and leaf_sph[] (set inside the kernel)
     uint32_t lds_nk, lds_sph;
@@ -722,6 +724,37 @@ ORT_FN float4 fetch_sphere(const KScene& S, int e) {
 #endif
 }
 
+// The 16-byte leaf records (KScene::leaf16) of the depth <= 8 camera walk's inline leaf children
+// (leaf_kids): one per node id, derived once per scene from node[] and leaf_sph[].
+//   inline form: a leaf holding exactly one sphere whose r^2 is +0 .. +inf (sign bit clear, not
+//                NaN) carries that sphere's leaf_sph entry {cx, cy, cz, r^2} itself, so the
+//                record's load is the sphere's;
+//   list form:   every other leaf carries {objectsOffset, objectCount, 0, 0x80000000 | count}:
+//                its node record, tagged by the sign bit of .w (r * r is never negative).
+// rec: the node's record; sp: leaf_sph[rec.x] of a one-sphere leaf (else unused).  Internal nodes
+// get the list form of their record; the walk never reads it.
+constexpr uint32_t kLeaf16ListTag = 0x80000000u;
+// hitEntry of a hit in an inline-form leaf while the walk runs: the leaf's node id with this
+// bit (16-byte records under the buffer loads' 4 GiB: ids and entries stay below 2^28);
+// traverse_fast_t turns it into the leaf's entry, node[id].x, after the walk
+constexpr int kLeafIdFlag = 0x40000000;
+ORT_FN bool leaf16_is_inline(uint2 rec, uint4 sp) {
+    return rec.y == 1u && (sp.w & 0x7fffffffu) <= 0x7f800000u && !(sp.w >> 31);
+}
+ORT_FN uint4 leaf16_record(uint2 rec, uint4 sp) {
+    return leaf16_is_inline(rec, sp) ? sp : make_uint4(rec.x, rec.y, 0u, kLeaf16ListTag | rec.y);
+}
+ORT_FN uint4 fetch_leaf16(const KScene& S, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // the array's true size in the descriptor: an index outside it reads zeros, not memory
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)S.leaf16, 0, (int)S.leaf16_bytes, 0x00020000);
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, (uint32_t)i * 16u, 0, 0);
+    return make_uint4(v[0], v[1], v[2], v[3]);
+#else
+    return S.leaf16[i];
+#endif
+}
+
 // The rejected-sphere skip's kid entry of a popped node loaded in the pop beside its record
 // (its latency hidden behind the pop's plane reads) instead of in the node's step.
 #ifndef ORT_KID_PREFETCH
@@ -770,6 +803,15 @@ struct Masks64 {  // levels 0..7: trees of depth <= 8
 #endif
     static constexpr bool kPopTable = ORT_POP_TABLE;
     static_assert(!kPopTable || kInlineLeaves, "the pop table has no level-D entries");
+    // a leaf child's record read from KScene::leaf16 (leaf16_record): a one-sphere leaf's
+    // sphere comes with it, so the sphere's own load, which nothing in the wave overlaps,
+    // is gone for such a leaf (leaf_kids); 0: the record from node[], every sphere from
+    // leaf_sph[].  Not with the rejected-sphere skip, which wants a rejected leaf's entry.
+#ifndef ORT_LEAF_INLINE
+#define ORT_LEAF_INLINE 1
+#endif
+    static constexpr bool kLeafInline = ORT_LEAF_INLINE;
+    static_assert(!kLeafInline || (kInlineLeaves && !kKidSkip), "leaf16 records: the inline leaf children, no skip");
     uint64_t m;
     ORT_FN void clear() { m = 0; }
     ORT_FN bool empty() const { return m == 0; }
@@ -804,6 +846,7 @@ struct Masks96 {  // levels 0..9 (ORT_COMPACT_MAX_DEPTH 10)
 #define ORT_INLINE_LEAVES_DEEP 0
 #endif
     static constexpr bool kInlineLeaves = ORT_INLINE_LEAVES_DEEP;
+    static constexpr bool kLeafInline = false;  // (KScene::leaf16 is built for depth <= 8 only)
 #ifndef ORT_PRE_MID_DEEP
 #define ORT_PRE_MID_DEEP 0
 #endif
@@ -975,6 +1018,7 @@ struct Masks96Lean : Masks96 {
 // (inline leaves pay off on coherent camera rays, not on scattered bounce rays).
 struct Masks64Plain : Masks64 {
     static constexpr bool kInlineLeaves = false;
+    static constexpr bool kLeafInline = false;
     static constexpr bool kPopTable = false;  // pops level-D leaves, which the table does not hold
     static constexpr bool kPreMid = false;
     static constexpr bool kKidSkip = true;
@@ -1107,6 +1151,14 @@ ORT_FN bool fast_begin(const KScene& S, const float* planes, const uint8_t* rank
     return fmin3(st.tFA, st.tFB, st.tFC) >= fmax3(st.tNA, st.tNB, st.tNC);
 }
 
+#if ORT_ANALYSIS
+// analysis library, host walks only (ort_debug_leaf_forms): sphere tests and accepted hits of
+// the kLeafInline walk per record form: {inline tests, inline hits, list tests, list hits}
+// (g_leaf_list_call: leaf_tests is running a list-form record of leaf16_tests)
+inline unsigned long long g_leaf_forms[4];
+inline bool g_leaf_list_call = false;
+#endif
+
 // Sphere_hit over one leaf's objects (glsl:327-338) in the range (ntmin, closest); returns
 // true if one was accepted (the walk then ends after this leaf).
 template <bool COUNT, class Masks>
@@ -1127,7 +1179,14 @@ ORT_FN bool leaf_tests(const KScene& S, FastStateT<Masks>& st, int off, int n, f
 #endif
         if (COUNT) cnt.v[2] += 1;
         float t;
-        if (sphere_hit_fast(r, a, st.ya, sp, ntmin, st.closest, t)) {
+        const bool h = sphere_hit_fast(r, a, st.ya, sp, ntmin, st.closest, t);
+#if ORT_ANALYSIS && !defined(__HIP_DEVICE_COMPILE__)
+        if (g_leaf_list_call) {
+            g_leaf_forms[2] += 1;
+            g_leaf_forms[3] += h ? 1 : 0;
+        }
+#endif
+        if (h) {
             st.closest = t;
             st.hitEntry = off + i;
             if (COUNT) cnt.v[3] += 1;
@@ -1184,11 +1243,46 @@ ORT_FN uint32_t child_drops(float tNA, float tNB, float tMA, float tMB, float tF
     return drop;
 }
 
+// leaf_tests for the inline leaf child `kid` given its leaf16 record lr (Masks::kLeafInline; never
+// with the rejected-sphere skip: Masks64's static_assert).  An inline-form record is the leaf's
+// one sphere, tested at once; a list-form one names the leaf's entries, tested by leaf_tests as
+// before.  (One sphere loop for both forms, an inline record as its single trip without the load,
+// was 2.8 % slower than no leaf records at all at C3: profiles/leaf_inline/ab.md.)
+template <class Masks>
+ORT_FN bool leaf16_tests(const KScene& S, FastStateT<Masks>& st, int kid, uint4 lr, float ntmin, Counters& cnt) {
+    if (!(lr.w >> 31)) {
+        const Ray r = st.ray();
+        const float a = dot(r.d, r.d);  // as fast_begin computed it
+        float t;
+        const bool h = sphere_hit_fast(r, a, st.ya, make_float4(u2f(lr.x), u2f(lr.y), u2f(lr.z), u2f(lr.w)), ntmin,
+                                       st.closest, t);
+#if ORT_ANALYSIS && !defined(__HIP_DEVICE_COMPILE__)
+        g_leaf_forms[0] += 1;
+        g_leaf_forms[1] += h ? 1 : 0;
+#endif
+        if (h) {
+            st.closest = t;
+            st.hitEntry = kid | kLeafIdFlag;
+        }
+        return st.hit();
+    }
+#if ORT_ANALYSIS && !defined(__HIP_DEVICE_COMPILE__)
+    g_leaf_list_call = true;
+    const bool hl = leaf_tests<false>(S, st, (int)lr.x, (int)lr.y, ntmin, cnt);
+    g_leaf_list_call = false;
+    return hl;
+#else
+    return leaf_tests<false>(S, st, (int)lr.x, (int)lr.y, ntmin, cnt);
+#endif
+}
+
 // The surviving leaf children (keep, rank-reversed bits) of a leaf-children node whose
 // children start at co, tested in rank order -- the order the reference pops them -- each
 // with the tmin the reference pushed for it (max(max3(child entries), t_min), t_min folded
 // into the C entries nN / nF; max is exact, so the order does not matter).  A hit ends the
 // walk after its leaf (glsl:336): no later sibling is tested.  Returns whether one hit.
+// Masks::kLeafInline (not the counting kernels, which keep the reference's loads): the child's
+// record comes from S.leaf16 instead of S.node (leaf16_tests).
 template <bool COUNT, class Masks>
 ORT_FN bool leaf_kids(const KScene& S, FastStateT<Masks>& st, int co, uint32_t keep, float tNA, float tMA, float tNB,
                       float tMB, float nN, float nF, Counters& cnt) {
@@ -1197,7 +1291,16 @@ ORT_FN bool leaf_kids(const KScene& S, FastStateT<Masks>& st, int co, uint32_t k
         const int hb = 31 - __builtin_clz(todo);
         todo ^= 1u << hb;
         const uint32_t R = 7u - (uint32_t)hb;
-        const uint2 lrec = fetch_node(S, co + (int)((st.otab >> (4 * R)) & 15u));
+        const int kid = co + (int)((st.otab >> (4 * R)) & 15u);
+        constexpr bool kRec16 = !COUNT && Masks::kLeafInline;
+        uint4 lr = make_uint4(0u, 0u, 0u, 0u);
+        if constexpr (kRec16) {
+            lr = fetch_leaf16(S, kid);
+        } else {
+            const uint2 lrec = fetch_node(S, kid);
+            lr.x = lrec.x;
+            lr.y = lrec.y;
+        }
         if (COUNT) cnt.v[0] += 1;
 #if defined(__HIP_DEVICE_COMPILE__)
         // bitwise selects (v_bfe_i32 + v_bfi_b32) in one asm block: the compiler turns a
@@ -1214,7 +1317,10 @@ ORT_FN bool leaf_kids(const KScene& S, FastStateT<Masks>& st, int co, uint32_t k
 #else
         const float eA = (R & 2u) ? tMA : tNA, eB = (R & 1u) ? tMB : tNB, eC = (R & 4u) ? nF : nN;
 #endif
-        const bool h = leaf_tests<COUNT>(S, st, (int)lrec.x, (int)lrec.y, fmax3(eA, eB, eC), cnt);
+        const float ntmin = fmax3(eA, eB, eC);
+        bool h;
+        if constexpr (kRec16) h = leaf16_tests(S, st, kid, lr, ntmin, cnt);
+        else h = leaf_tests<COUNT>(S, st, (int)lr.x, (int)lr.y, ntmin, cnt);
         todo = h ? 0u : todo;
     }
     return st.hit();
@@ -1450,6 +1556,11 @@ ORT_FN bool traverse_fast_t(const KScene& S, const float* planes, const uint8_t*
     if (walked) *walked = st.ray();
     if (!in) return false;
     hitEntry = st.hitEntry;
+    if constexpr (!COUNT && Masks::kLeafInline) {
+        // a hit in an inline-form leaf left the leaf's node id (leaf16_tests): its entry -- what
+        // shading reads leaf_idx[] by -- is its record's offset, one load per hit ray
+        if (hitEntry >= kLeafIdFlag) hitEntry = (int)fetch_node(S, hitEntry ^ kLeafIdFlag).x;
+    }
     hitT = st.closest;
     return st.hit();
 }
