@@ -12,7 +12,7 @@ HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -ffp-contract=off -fno-fast-ma
 HOST_SRCS := octree.cpp scene.cpp host_abi.cpp layout.cpp raytracer.cpp
 HOST_OBJS := $(addprefix $(OBJ)/,$(HOST_SRCS:.cpp=.o))
 HIP_OBJS := $(OBJ)/ort_kernel.o $(OBJ)/gpu_build.o $(OBJ)/group.o
-HDRS := $(wildcard $(SRC)/*.h) $(SRC)/prebuilt_scene.inc $(SRC)/ray_query.inc $(SRC)/accum.inc $(SRC)/camera_query.inc $(SRC)/ray_modes.inc $(SRC)/radiance_query.inc $(SRC)/host_emulation.inc include/ort.h include/ort_math.h
+HDRS := $(wildcard $(SRC)/*.h) $(SRC)/prebuilt_scene.inc $(SRC)/ray_query.inc $(SRC)/accum.inc $(SRC)/camera_query.inc $(SRC)/ray_modes.inc $(SRC)/radiance_query.inc $(SRC)/denoise.inc $(SRC)/host_emulation.inc include/ort.h include/ort_math.h
 
 # The analysis library (test/analysis surface: ort_debug_* host emulation and walk statistics,
 # ORT_OPT_DEBUG_FLAGS) -- the same sources with -DORT_ANALYSIS=1; the CPU suite and tools/
@@ -55,7 +55,10 @@ $(LIB): $(HOST_OBJS) $(HIP_OBJS)
 	@mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -ldl -Wl,-soname,libort.so
 
-examples: build/ort_main build/stats_row build/trace_rays build/progressive build/pick build/visibility build/radiance_probe
+examples: build/ort_main build/stats_row build/trace_rays build/progressive build/pick build/visibility build/radiance_probe build/denoise
+
+build/denoise: tests/cpp/denoise.cpp $(LIB) $(HDRS)
+	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ tests/cpp/denoise.cpp -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
 
 build/radiance_probe: tests/cpp/radiance_probe.cpp $(LIB) $(HDRS)
 	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ tests/cpp/radiance_probe.cpp -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
@@ -94,12 +97,13 @@ SAN_HOST := $(addprefix $(SANOBJ)/,$(HOST_SRCS:.cpp=.o))
 SAN_HIP := $(SANOBJ)/ort_kernel.o $(SANOBJ)/gpu_build.o $(SANOBJ)/group.o
 HIP_SAN := $(foreach f,address undefined,-Xarch_host -fsanitize=$(f)) -Xarch_host -fno-sanitize-recover=undefined
 
-san: build/san/san_check build/san/san_query build/san/san_camera build/san/san_query_modes build/san/san_radiance
+san: build/san/san_check build/san/san_query build/san/san_camera build/san/san_query_modes build/san/san_radiance build/san/san_denoise
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/san_check
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/san_query
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/san_camera
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/san_query_modes
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/san_radiance
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/san_denoise
 
 $(SANOBJ)/%.o: $(SRC)/%.cpp $(HDRS)
 	@mkdir -p $(SANOBJ)
@@ -136,6 +140,14 @@ $(SANOBJ)/san_query_modes.o: tests/cpp/san_query_modes.cpp $(HDRS)
 $(SANOBJ)/san_radiance.o: tests/cpp/san_radiance.cpp $(HDRS)
 	@mkdir -p $(SANOBJ)
 	$(CLANGXX) $(SAN) -std=c++17 -I$(SRC) -c $< -o $@
+
+# the denoiser's host code (ort_debug_denoise: denoise.inc denoise_pixel) likewise
+$(SANOBJ)/san_denoise.o: tests/cpp/san_denoise.cpp $(HDRS)
+	@mkdir -p $(SANOBJ)
+	$(CLANGXX) $(SAN) -std=c++17 -I$(SRC) -c $< -o $@
+
+build/san/san_denoise: $(SANOBJ)/san_denoise.o $(SAN_HOST) $(SAN_HIP)
+	$(HIPCC) --offload-arch=$(ARCH) $(SAN) -o $@ $^ -ldl
 
 build/san/san_radiance: $(SANOBJ)/san_radiance.o $(SAN_HOST) $(SAN_HIP)
 	$(HIPCC) --offload-arch=$(ARCH) $(SAN) -o $@ $^ -ldl

@@ -722,6 +722,70 @@ int ort_camera_view(const float position[3], const float world_up[3], float yaw_
 /* Library version string. */
 const char* ort_version(void);
 
+/* ---- guided denoiser for few-sample previews: an edge-avoiding a-trous wavelet filter ------------
+ * ort_denoise filters a rows x width RGB32F image with the edge-avoiding a-trous filter of Dammertz
+ * et al. 2010, guided by what ort_trace_camera writes for the same pixels: the hit records
+ * (t, sphere) and the normals.  It is made for the one-sample picture of a progressive preview
+ * (ort_accum_render) while the camera moves: with many samples per pixel the filter blurs more than
+ * it removes, unless the colour term is on.  It needs no scene and reads and writes no render,
+ * accumulation or query state.
+ * The arithmetic, every operation one float32 operation in this order (no contraction).  Iteration
+ * i = 0 .. iterations-1 has step s = 2^i, reads the previous iteration's colours cur (the input for
+ * i = 0) and writes new ones.  For pixel p the taps are q = p + s (dx, dy), dy = -2 .. 2 outside,
+ * dx = -2 .. 2 inside, the centre at its place; taps outside the image are skipped.  With
+ * h = (1/16, 1/4, 3/8, 1/4, 1/16):
+ *     w = h[dy+2] * h[dx+2]
+ *     if p and q are hits (sphere >= 0):
+ *         a = clamp01((n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z); normal_power times: a = a * a;  w *= a
+ *         if sigma_depth > 0: w *= clamp01(1 - |t_p - t_q| * inv_z),  inv_z = 1 / (sigma_depth * (float)s)
+ *     if sigma_color > 0: d = cur_p - cur_q; dc = (d.r d.r + d.g d.g) + d.b d.b;
+ *         wc = clamp01(1 - dc * inv_c); w *= wc * wc,  inv_c = 1 / (sc * sc), sc = sigma_color * 2^-i
+ *     the tap adds nothing (w = 0, and a non-finite cur_q is not multiplied) if exactly one of p and
+ *         q is a hit, or ORT_DENOISE_SAME_SPHERE is set and the sphere ids differ, or cur_q has a
+ *         non-finite channel
+ *     sw += w; sum += w * cur_q per channel, in tap order;  next_p = sum / sw per channel
+ * clamp01(x) is x < 0 ? 0 : (x > 1 ? 1 : x).  A pixel whose own cur_p has a non-finite channel is
+ * copied through unchanged.  The last iteration's result is the output: as is for
+ * ORT_FORMAT_RGB32F, through the render path's quantiser for ORT_FORMAT_RGBA8.
+ *   color     the image, row r at color + r * color_pitch_bytes.
+ *   hits, normals  rows * width records, tight, as ort_trace_camera writes them for the tile.
+ *   output    any ort_output with ORT_PLACE_TILE (the tile is the image): both formats, with or
+ *             without a pitch.  output->data == color (in place: RGB32F, the same pitch) is allowed
+ *             for every iterations value: the input is read completely before the output is written.
+ *   border    a tile denoised alone differs from the same pixels of the whole frame's filter within
+ *             2 (2^iterations - 1) pixels of its border: the taps past the border are skipped, not
+ *             mirrored.
+ * on_device, the stream rules and the staging of host pointers (grow-only buffers the context owns,
+ * the denoiser's own, separate from the queries') are ort_trace_rays'.  Denoises of one context
+ * share those buffers: the caller orders them among themselves.  width * rows == 0: ORT_OK, nothing
+ * launched.  ORT_ERR_INVALID_ARG, before anything is launched and with the output untouched: NULL
+ * arguments, negative sizes or more than 2^30 pixels, iterations outside 1 .. 6, normal_power
+ * outside 0 .. 7, a negative or NaN sigma, unknown flags, reserved != 0, pointers that are not
+ * 4-byte aligned, a color_pitch_bytes that is not 0 or a multiple of 4 of at least 12 * width and
+ * below 2^31, ORT_PLACE_FRAME, an output that ort_render_ex refuses, on_device disagreeing with
+ * output->is_device.  Not in scope: variance-guided colour weights (they need a sum of squares in
+ * the accumulation state), albedo demodulation, temporal reprojection, denoising on an ort_group,
+ * banded tiles (their rows are not neighbours in the frame). */
+#define ORT_DENOISE_SAME_SPHERE 1   /* a tap of another sphere id (a miss among them) adds nothing */
+typedef struct ort_denoise_desc {
+    const float*       color;             /* RGB32F, row r at color + r * color_pitch_bytes */
+    int64_t            color_pitch_bytes; /* 0: tight (12 * width); else a multiple of 4, >= 12 * width, < 2^31 */
+    const ort_ray_hit* hits;              /* rows * width records, tight (ort_trace_camera's) */
+    const float*       normals;           /* 3 floats per pixel, tight */
+    int32_t width, rows;
+    int32_t on_device;                    /* color, hits, normals are device pointers; output->is_device must agree */
+    int32_t iterations;                   /* 1 .. 6 */
+    float   sigma_color, sigma_depth;     /* 0: term off */
+    int32_t normal_power;                 /* 0 .. 7 */
+    int32_t flags;                        /* 0 or ORT_DENOISE_SAME_SPHERE */
+    int32_t reserved[2];                  /* 0 */
+} ort_denoise_desc;
+int ort_denoise(ort_ctx* ctx, const ort_denoise_desc* d, const ort_output* output, void* stream);
+/* Duration in milliseconds of the last ort_denoise's kernels (the pack pass and the iterations; the
+ * host copies not), from HIP events on its stream.  Only valid once that stream has passed it.
+ * ORT_ERR_INVALID_ARG: NULL arguments, or no ort_denoise has launched anything on ctx yet. */
+int ort_last_denoise_ms(ort_ctx* ctx, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

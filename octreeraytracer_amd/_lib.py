@@ -70,6 +70,7 @@ EXPORTED_SYMBOLS = (
     "ort_trace_camera",
     "ort_trace_rays_ex",
     "ort_trace_radiance",
+    "ort_denoise", "ort_last_denoise_ms",
 )
 ORT_GROUP_TRANSPORT_RCCL = 0
 ORT_GROUP_TRANSPORT_COPY = 1
@@ -95,6 +96,8 @@ CAMERA_RAYS = {"first_sample": ORT_CAMERA_FIRST_SAMPLE, "pixel_centre": ORT_CAME
 # ort_radiance_query.flags (ort_trace_radiance), beside ORT_QUERY_SORT
 ORT_RADIANCE_NORMALIZE = 2
 ORT_RADIANCE_GAMMA = 4
+# ort_denoise_desc.flags (ort_denoise)
+ORT_DENOISE_SAME_SPHERE = 1
 
 
 class OrtParams(C.Structure):
@@ -153,6 +156,15 @@ class OrtRadianceQuery(C.Structure):
     ]
 
 
+class OrtDenoiseDesc(C.Structure):
+    _fields_ = [
+        ("color", C.c_void_p), ("color_pitch_bytes", C.c_int64), ("hits", C.c_void_p), ("normals", C.c_void_p),
+        ("width", C.c_int32), ("rows", C.c_int32), ("on_device", C.c_int32), ("iterations", C.c_int32),
+        ("sigma_color", C.c_float), ("sigma_depth", C.c_float), ("normal_power", C.c_int32), ("flags", C.c_int32),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
 class OrtSceneInfo(C.Structure):
     _fields_ = [
         ("n_spheres", C.c_int32), ("n_nodes", C.c_int32), ("n_indices", C.c_int64),
@@ -202,6 +214,9 @@ def _declare(lib, debug: str = "none"):
         "ort_trace_rays_ex": (C.c_int, [_vp, C.POINTER(OrtRayQueryEx), _vp]),
         "ort_trace_camera": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(OrtCameraQuery), _vp]),
         "ort_trace_radiance": (C.c_int, [_vp, C.POINTER(OrtRadianceQuery), _vp]),
+        "ort_denoise": (C.c_int, [_vp, C.POINTER(OrtDenoiseDesc), C.POINTER(OrtOutput), _vp]),
+        "ort_last_denoise_ms": (C.c_int, [_vp, _fp]),
+        "ort_debug_denoise": (C.c_int, [C.POINTER(OrtDenoiseDesc), C.POINTER(OrtOutput)]),
         "ort_accum_begin": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(_vp)]),
         "ort_accum_render": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(OrtOutput), _vp]),
         "ort_accum_restart": (C.c_int, [_vp, _vp, C.POINTER(OrtParams)]),
@@ -269,8 +284,9 @@ def _declare(lib, debug: str = "none"):
     for name, (res, args) in sig.items():
         if name.startswith("ort_debug_") and (debug == "none" or (debug == "present" and not hasattr(lib, name))):
             continue
-        if name in ("ort_trace_camera", "ort_trace_rays_ex", "ort_trace_radiance") and debug == "present" and not hasattr(lib, name):
-            continue  # an ORT_LIB override of a build from before these queries (A/B runs): calling it raises
+        if name in ("ort_trace_camera", "ort_trace_rays_ex", "ort_trace_radiance", "ort_denoise",
+                    "ort_last_denoise_ms") and debug == "present" and not hasattr(lib, name):
+            continue  # an ORT_LIB override of a build from before these calls (A/B runs): calling it raises
         f = getattr(lib, name)
         f.restype = res
         f.argtypes = args

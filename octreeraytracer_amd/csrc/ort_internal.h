@@ -104,6 +104,11 @@ int ort_debug_radiance_rays(const float* sphere_center_radius, const float* sphe
                             int64_t n_indices, int32_t layout, int32_t use_octree, const float* rays,
                             const float* states, int64_t n_rays, int32_t max_depth, int32_t paths, int32_t flags,
                             float* radiance, float* states_out);
+// TEST-ONLY: ort_denoise on the host CPU: the pack pass and every iteration through denoise.inc's
+// denoise_pixel, the kernels' own per-pixel function, one pixel after another.  d's pointers and
+// output->data are host pointers (d->on_device and output->is_device 0); what ort_denoise refuses
+// is refused here, with the output untouched.
+int ort_debug_denoise(const ort_denoise_desc* d, const ort_output* output);
 // ANALYSIS-ONLY: lane overlap of sampled 8x8 primary-ray blocks (tools/wave_stats.py).
 int ort_debug_wave_stats(const float* sphere_center_radius, const float* sphere_mat_albedo,
                          const float* sphere_fuzz_ri, int32_t n_spheres, const float* node_min,

@@ -1902,6 +1902,16 @@ struct QueryState {
     bool timed = false;
 };
 
+// The denoiser's own state (ort_denoise: denoise.inc), none of the queries' or the pipeline's: the
+// staging of host arrays and of a host output (grow-only), the packed guide records, the two
+// colour buffers the iterations ping-pong between, the timing events of the last denoise.
+struct DenoiseState {
+    DevBuf in_color, in_hits, in_normals, out;
+    DevBuf guide, col_a, col_b;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;
+};
+
 }  // namespace
 
 #ifndef ORT_HEAVY_STEPS
@@ -2052,6 +2062,7 @@ struct ort_ctx {
     DevBuf key_spread;            // its origin-code tables for the scene's root box (path_key.h)
     float spread_box[6] = {0, 0, 0, 0, 0, 0};  // the root box key_spread was built for
     QueryState query;  // ray, camera and mode queries (ray_query.inc)
+    DenoiseState denoise;  // ort_denoise (denoise.inc)
     // accumulations (ort_accum_*, accum.inc): the live ones, each with its own state, counters and
     // events (ort_destroy frees what is left), and the scene's generation: free_scene advances
     // it, and an accumulation begun or restarted under another one is stale
@@ -2109,6 +2120,13 @@ void free_query(QueryState& q) {
     if (q.ev0) (void)hipEventDestroy(q.ev0);
     if (q.ev1) (void)hipEventDestroy(q.ev1);
     q = QueryState{};
+}
+
+void free_denoise(DenoiseState& d) {
+    for (DevBuf* b : {&d.in_color, &d.in_hits, &d.in_normals, &d.out, &d.guide, &d.col_a, &d.col_b}) free_buf(*b);
+    if (d.ev0) (void)hipEventDestroy(d.ev0);
+    if (d.ev1) (void)hipEventDestroy(d.ev1);
+    d = DenoiseState{};
 }
 
 // The scene's device buffers (C: ort_ctx or const ort_ctx): the one list free_scene frees and
@@ -3461,6 +3479,7 @@ int ort_destroy(ort_ctx* ctx) {
                       &ctx->pcost, &ctx->bcost, &ctx->hbits, &ctx->hlist, &ctx->hcnt, &ctx->pplist, &ctx->ppcnt, &ctx->ppcost, &ctx->spst, &ctx->spcol, &ctx->spfix, &ctx->spfixn};
     for (DevBuf* b : pipe) free_buf(*b);
     free_query(ctx->query);
+    free_denoise(ctx->denoise);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (int i = 0; i < ort_ctx::kRing; ++i)
@@ -3729,3 +3748,6 @@ int ort_count_traffic(ort_ctx* ctx, const ort_params* params, const ort_tile* ti
 #include "ray_modes.inc"
 // Radiance queries (ort_trace_radiance, ort_debug_radiance_rays): last, so that every earlier kernel keeps its place.
 #include "radiance_query.inc"
+
+// the denoiser (ort_denoise): its kernels follow every other kernel in the code object
+#include "denoise.inc"

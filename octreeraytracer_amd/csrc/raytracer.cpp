@@ -1,6 +1,7 @@
 // raytracer.cpp -- Raytracer on the gfx950 kernel (see raytracer.h).
 #include "raytracer.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -106,6 +107,9 @@ void Raytracer::setupBuffers() {
 void Raytracer::cleanupBuffers() {
     if (dframe) (void)hipFree(dframe);
     dframe = nullptr;
+    if (dguides) (void)hipFree(dguides);
+    dguides = nullptr;
+    dguidesBytes = 0;
     accum = nullptr;  // (ort_destroy frees it)
     if (ctx) ort_destroy(ctx);
     if (group) ort_group_destroy(group);
@@ -255,6 +259,65 @@ int Raytracer::renderProgressive(const Camera& cam, int samples, float* rgb, int
     ort_accum_info info{};
     if (samplesDone && ort_accum_get_info(accum, &info) == ORT_OK) *samplesDone = info.samples_done;
     return rc;
+}
+
+int Raytracer::denoise(const Camera& cam, const ort_tile& tile, const float* rgb, const ort_output& output,
+                       const DenoiseOptions& options) {
+    if (!ctx && !group && !initialize()) return ORT_ERR_HIP;
+    if (group) return ORT_ERR_UNSUPPORTED;  // the denoiser runs on one context
+    if (tile.width < 0 || tile.rows < 0 || tile.y0 < 0 || (tile.band_height > 0 && tile.rows > tile.band_height))
+        return ORT_ERR_INVALID_ARG;  // rows that are not neighbours in the frame
+    // rows with y >= height are neither filtered nor used as taps (as Renderer.denoise)
+    const int real = std::max(0, std::min(tile.rows, height - tile.y0));
+    const size_t n = (size_t)tile.width * (size_t)tile.rows;
+    std::vector<ort_ray_hit> hits;
+    std::vector<float> normals;
+    ort_camera_query q = {nullptr, nullptr, nullptr, output.is_device ? 1 : 0, ORT_CAMERA_PIXEL_CENTRE, {0, 0}};
+    if (output.is_device) {
+        if (dguidesBytes < 20 * n) {
+            if (dguides) (void)hipFree(dguides);
+            dguides = nullptr;
+            dguidesBytes = 0;
+            if (hipSetDevice(cfg.device) != hipSuccess || hipMalloc(&dguides, 20 * n) != hipSuccess) return ORT_ERR_OUT_OF_MEMORY;
+            dguidesBytes = 20 * n;
+        }
+        q.hits = static_cast<ort_ray_hit*>(dguides);
+        q.normals = reinterpret_cast<float*>(static_cast<unsigned char*>(dguides) + 8 * n);
+    } else {
+        hits.resize(n);
+        normals.resize(3 * n);
+        q.hits = hits.data();
+        q.normals = normals.data();
+    }
+    if (n > 0) {
+        const int rc = traceCamera(cam, tile, q);
+        if (rc != ORT_OK) return rc;
+    }
+    ort_denoise_desc d;
+    std::memset(&d, 0, sizeof d);
+    d.color = rgb;
+    d.hits = q.hits;
+    d.normals = q.normals;
+    d.width = tile.width;
+    d.rows = real;
+    d.on_device = q.on_device;
+    d.iterations = options.iterations;
+    d.sigma_color = options.sigmaColor;
+    d.sigma_depth = options.sigmaDepth;
+    d.normal_power = options.normalPower;
+    d.flags = options.sameSphere ? ORT_DENOISE_SAME_SPHERE : 0;
+    const int rc = ort_denoise(ctx, &d, &output, nullptr);
+    if (rc != ORT_OK || real == tile.rows || !output.data) return rc;
+    // the padding rows as render writes them: zero bytes
+    const size_t rowBytes = (size_t)tile.width * (output.format == ORT_FORMAT_RGBA8 ? 4 : 12);
+    const size_t pitch = output.row_pitch_bytes ? (size_t)output.row_pitch_bytes : rowBytes;
+    unsigned char* first = static_cast<unsigned char*>(output.data) + (size_t)real * pitch;
+    if (output.is_device) {
+        if (hipMemset2D(first, pitch, 0, rowBytes, (size_t)(tile.rows - real)) != hipSuccess) return ORT_ERR_HIP;
+    } else {
+        for (int j = real; j < tile.rows; ++j) std::memset(first + (size_t)(j - real) * pitch, 0, rowBytes);
+    }
+    return ORT_OK;
 }
 
 int Raytracer::render(const Camera& cam, float* rgb) {

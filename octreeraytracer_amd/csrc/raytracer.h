@@ -60,6 +60,15 @@ struct StatsWork {
     int hostCores = 1;
 };
 
+// Raytracer::denoise's parameters (include/ort.h ort_denoise_desc): the library's defaults.
+struct DenoiseOptions {
+    int iterations = 3;        // 1 .. 6: steps 1, 2, 4, ...
+    float sigmaColor = 0.0f;   // 0: the colour term off
+    float sigmaDepth = 0.0f;   // 0: the depth term off
+    int normalPower = 5;       // squarings of the clamped dot product of the normals, 0 .. 7
+    bool sameSphere = true;    // taps never cross from one sphere (or the sky) to another
+};
+
 class Raytracer {
 public:
     Raytracer();
@@ -128,6 +137,17 @@ public:
     // in the picture.  Single-device configurations only (a group: ORT_ERR_UNSUPPORTED).
     int renderProgressive(const Camera& cam, int samples, float* rgb, int* samplesDone = nullptr);
 
+    // The guided denoiser for few-sample previews (include/ort.h ort_denoise): filters the tile's
+    // picture rgb (tight RGB32F rows, as render and renderProgressive write them) into output, any
+    // ort_output with ORT_PLACE_TILE; rgb is host or device memory as output.is_device says, and
+    // output.data may be rgb itself.  The guides are cam's pixel-centre camera query of the tile
+    // (ORT_CAMERA_PIXEL_CENTRE, normals), traced here.  The tile must be one band
+    // (ORT_ERR_INVALID_ARG otherwise); rows with y >= height are neither filtered nor used as taps
+    // and come out as render writes them (zeros), as in Renderer.denoise.  Synchronous; single-device configurations only (a
+    // group: ORT_ERR_UNSUPPORTED).
+    int denoise(const Camera& cam, const ort_tile& tile, const float* rgb, const ort_output& output,
+                const DenoiseOptions& options = {});
+
     Camera camera;  // the reference keeps a global Camera (src/main.cpp:18); pose set like main()
     const RaytracerConfig& config() const { return cfg; }
     const std::vector<Sphere>& getSpheres() const { return spheres; }
@@ -164,6 +184,8 @@ private:
     std::vector<double> renderTimes;
     std::vector<float> frame;
     float* dframe = nullptr;       // run()'s device frame (readback off), on the context's device
+    void* dguides = nullptr;       // denoise's guides for device pictures (20 bytes a pixel, grow-only)
+    size_t dguidesBytes = 0;
     int renderRun();               // one frame of run(): into dframe, or into `frame` with readback
     ort_accum* accum = nullptr;    // renderProgressive's accumulation (the context owns it) and its camera
     ort_params accumParams{};

@@ -662,6 +662,81 @@ class Renderer:
         self._check(self._lib.ort_trace_radiance(self._ctx, C.byref(q), s))
         return (out, states_out) if want_states else out
 
+    # -- denoiser ---------------------------------------------------------------------
+    def denoise(self, image, guides=None, *, params: FrameParams | None = None, tile: Tile | None = None,
+                iterations: int = 3, sigma_color: float = 0.0, sigma_depth: float = 0.0, normal_power: int = 5,
+                same_sphere: bool = True, format: str = "rgb32f", row_pitch: int | None = None, out=None, stream=None):
+        """Filter a few-sample picture with the guided a-trous filter (ort_denoise, include/ort.h):
+        `iterations` passes of a 5x5 B3-spline kernel with step 1, 2, 4, ..., whose taps are weighted
+        by the guides -- normals (normal_power squarings of the clamped dot product), depth
+        (sigma_depth > 0) and, with sigma_color > 0, the colours themselves -- and, with same_sphere,
+        never cross from one sphere (or the sky) to another.  Made for the one-sample preview of a
+        moving camera; with many samples it blurs more than it removes unless sigma_color is on.
+
+        image: (rows, width, 3) float32, a numpy array or a torch CUDA tensor on this device (then
+        everything stays there); rows may be a pitch apart (a column slice of a wider array).
+        guides: (hits, normals) as ``trace_camera`` returns them for the same pixels -- hits an int32
+        array of {t bits, sphere} records or the pair (t, sphere), normals (rows, width, 3) float32
+        -- of the image's kind (numpy or tensors).  None: the pixel-centre guides of params and tile,
+        traced here (``trace_camera(params, tile, which="pixel_centre", normals=True)``).
+        params, tile: the frame and tile the image was rendered with.  A banded tile is refused: its
+        rows are not neighbours in the frame.  Rows with y >= height are neither filtered nor used
+        as taps and come out as ``render`` writes them (zeros).  Within 2 (2^iterations - 1) pixels
+        of the tile's border the result differs from the whole frame's filter.
+        format, row_pitch, out, stream: as ``render`` (place is "tile"); out may be the image itself
+        (in place).  Returns out."""
+        who = "denoise"
+        device = not isinstance(image, np.ndarray)
+        rows, width, pitch, color = _denoise_image(who, image, self.device if device else None)
+        real = rows
+        if tile is not None and params is None:
+            raise ValueError(f"{who}: tile needs params")
+        if params is not None:
+            tile = tile or Tile.full(params)
+            real = _denoise_tile_rows(who, params, tile, rows, width)
+        if guides is None:
+            if params is None:
+                raise ValueError(f"{who}: guides=None traces the guides of params (and tile): pass params")
+            if device:
+                import torch
+                dev = torch.device("cuda", self.device)
+                hits = torch.empty((rows, width, 2), dtype=torch.int32, device=dev)
+                nrm = torch.empty((rows, width, 3), dtype=torch.float32, device=dev)
+                self.trace_camera(params, tile, which="pixel_centre", normals=nrm, out=hits, stream=stream)
+            else:
+                t, sph, nrm = self.trace_camera(params, tile, which="pixel_centre", normals=True, stream=stream)
+                hits = (t, sph)
+            guides = (hits, nrm)
+        hits, nrm, keep = _denoise_guides(who, guides, rows, width, self if device else None)
+        if out is None and device:
+            import torch
+            fmt_t, ch = (torch.float32, 3) if format == "rgb32f" else (torch.uint8, 4)
+            if row_pitch is not None:
+                raise ValueError(f"{who}: row_pitch describes a caller's buffer: pass out")
+            out = torch.empty((rows, width, ch), dtype=fmt_t, device=torch.device("cuda", self.device))
+        if device and isinstance(out, np.ndarray):
+            raise ValueError(f"{who}: a device image needs a device out (a torch CUDA tensor or a pointer)")
+        if not device and out is not None and not isinstance(out, np.ndarray):
+            raise ValueError(f"{who}: a host image needs a numpy out")
+        o, out = self._output(who, None, Tile(0, width, 0, rows), out, format, row_pitch, "tile")
+        if real < rows and not isinstance(out, np.ndarray) and not hasattr(out, "numel"):
+            raise ValueError(f"{who}: a tile reaching past the frame needs out as a tensor (its padding rows are zeroed)")
+        d = _denoise_desc(color, pitch, hits, nrm, width, real, device, iterations, sigma_color, sigma_depth, normal_power,
+                          same_sphere)
+        s = C.c_void_p(int(stream)) if stream else None
+        self._check(self._lib.ort_denoise(self._ctx, C.byref(d), C.byref(o), s))
+        del keep
+        if real < rows:  # after the call: a refused one leaves out untouched
+            _denoise_zero_rows(who, out, real, rows, o.row_pitch_bytes or width * L.FORMAT_BPP[o.format],
+                               width * L.FORMAT_BPP[o.format], self.device if device else None)
+        return out
+
+    def last_denoise_ms(self) -> float:
+        """The last denoise's kernels (the pack pass and the iterations), from HIP events on its stream."""
+        ms = C.c_float()
+        self._check(self._lib.ort_last_denoise_ms(self._ctx, C.byref(ms)))
+        return ms.value
+
     def last_query_ms(self) -> float:
         """The last trace_rays', trace_camera's or trace_radiance's kernels (a sort included), from HIP events on its stream."""
         ms = C.c_float()
@@ -716,6 +791,7 @@ class Accumulation:
         self._r = renderer
         self._h = C.c_void_p()
         self.params, self.tile = params, tile
+        self._guides = None
         p, t = params.to_c(), tile.to_c()
         renderer._check(renderer._lib.ort_accum_begin(renderer._ctx, C.byref(p), C.byref(t), C.byref(self._h)))
 
@@ -776,6 +852,22 @@ class Accumulation:
         p = params.to_c()
         self._r._check(self._r._lib.ort_accum_restart(self._r._ctx, self._h, C.byref(p)))
         self.params = params
+        self._guides = None
+
+    def guides(self):
+        """The pixel-centre guides of the accumulation's params and tile for ``Renderer.denoise``:
+        (hits, normals), torch CUDA tensors (rows, width, 2) int32 {t bits, sphere} and (rows, width,
+        3) float32 -- ``trace_camera(params, tile, which="pixel_centre", normals=True)`` on the
+        device, traced once and kept until ``restart`` (a new camera) drops them."""
+        if self._guides is None:
+            import torch
+            dev = torch.device("cuda", self._r.device)
+            rows, width = int(self.tile.rows), int(self.tile.width)
+            hits = torch.empty((rows, width, 2), dtype=torch.int32, device=dev)
+            nrm = torch.empty((rows, width, 3), dtype=torch.float32, device=dev)
+            self._r.trace_camera(self.params, self.tile, which="pixel_centre", normals=nrm, out=hits)
+            self._guides = (hits, nrm)
+        return self._guides
 
     def last_pass_ms(self) -> float:
         """The last step's kernels, from HIP events on its stream."""
@@ -946,3 +1038,122 @@ def radiance_rays_host(spheres: SphereSet, tree: FlatOctree | None, rays, states
                                         flags, L.fptr(rad), L.fptr(st_out)))
     del keep
     return (rad, st_out) if st_out is not None else rad
+
+
+def _denoise_image(who, image, device):
+    """rows, width, the rows' pitch in bytes and the address of a (rows, width, 3) float32 image: a
+    numpy array, or (device: the GPU's index) a torch CUDA tensor; rows may be a pitch apart."""
+    if device is None:
+        if image.dtype != np.float32 or image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError(f"{who}: image must be a (rows, width, 3) float32 array (got {image.dtype}, shape {image.shape})")
+        rows, width = image.shape[:2]
+        strides, ptr = image.strides, image.ctypes.data
+    else:
+        if not hasattr(image, "data_ptr"):
+            raise ValueError(f"{who}: image must be a numpy array or a torch CUDA tensor")
+        if str(image.dtype) != "torch.float32" or image.dim() != 3 or image.shape[2] != 3:
+            raise ValueError(f"{who}: image must be a (rows, width, 3) float32 tensor (got {image.dtype}, shape {tuple(image.shape)})")
+        if image.device.type != "cuda" or image.device.index != device:
+            raise ValueError(f"{who}: image is on {image.device}, the context filters on cuda:{device}")
+        rows, width = int(image.shape[0]), int(image.shape[1])
+        strides, ptr = tuple(4 * int(v) for v in image.stride()), image.data_ptr()
+    if rows * width == 0:
+        return rows, width, 0, ptr
+    if (width > 1 and strides[1] != 12) or strides[2] != 4 or (rows > 1 and (strides[0] < 12 * width or strides[0] % 4)):
+        raise ValueError(f"{who}: image pixels must be 12 bytes apart and rows at least 12 * width (strides {strides})")
+    return rows, width, (strides[0] if rows > 1 else 12 * width), ptr
+
+
+def _denoise_tile_rows(who, params, tile, rows, width):
+    """The rows of the image that lie inside the frame; refuses a banded tile and a tile of another shape."""
+    if tile.band_height > 0 and tile.rows > tile.band_height:
+        raise ValueError(f"{who}: a banded tile's rows are not neighbours in the frame: denoise the assembled frame")
+    if (int(tile.rows), int(tile.width)) != (rows, width):
+        raise ValueError(f"{who}: image is {rows} x {width} but the tile is {tile.rows} x {tile.width}")
+    return max(0, min(rows, int(params.height) - int(tile.y0)))
+
+
+def _denoise_guides(who, guides, rows, width, renderer):
+    """(hits address, normals address, objects to keep alive) of guides = (hits or (t, sphere), normals);
+    renderer: None for numpy arrays, else the Renderer whose device the tensors live on."""
+    try:
+        hits, nrm = guides
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: guides must be (hits or (t, sphere), normals)") from None
+    n = rows * width
+    if renderer is None:
+        if isinstance(hits, (tuple, list)):
+            t, sph = hits
+            t, sph = np.ascontiguousarray(t, np.float32), np.ascontiguousarray(sph, np.int32)
+            if t.size != n or sph.size != n:
+                raise ValueError(f"{who}: t and sphere must hold {n} pixels each")
+            rec = np.empty((n, 2), np.int32)
+            rec[:, 0] = t.reshape(-1).view(np.int32)
+            rec[:, 1] = sph.reshape(-1)
+            hits = rec
+        if not isinstance(hits, np.ndarray) or hits.dtype != np.int32 or not hits.flags.c_contiguous or hits.size != 2 * n:
+            raise ValueError(f"{who}: hits must be a C-contiguous int32 array of {n} {{t bits, sphere}} records")
+        if (not isinstance(nrm, np.ndarray) or nrm.dtype != np.float32 or not nrm.flags.c_contiguous or nrm.size != 3 * n):
+            raise ValueError(f"{who}: normals must be a C-contiguous float32 array of 3 x {n} elements")
+        return hits.ctypes.data, nrm.ctypes.data, (hits, nrm)
+    if isinstance(hits, (tuple, list)):
+        import torch
+        t, sph = hits
+        if t.numel() != n or sph.numel() != n:
+            raise ValueError(f"{who}: t and sphere must hold {n} pixels each")
+        hits = torch.stack((t.contiguous().view(torch.int32).reshape(-1), sph.reshape(-1)), dim=1).contiguous()
+        torch.cuda.current_stream(renderer.device).synchronize()  # (made on torch's stream, read on the call's)
+    if hasattr(hits, "numel") and hits.numel() != 2 * n:
+        raise ValueError(f"{who}: hits must hold {n} {{t bits, sphere}} records")
+    if hasattr(nrm, "numel") and nrm.numel() != 3 * n:
+        raise ValueError(f"{who}: normals must hold 3 x {n} elements")
+    return (renderer._device_arg(who, hits, "hits", "int32", 8 * n),
+            renderer._device_arg(who, nrm, "normals", "float32", 12 * n), (hits, nrm))
+
+
+def _denoise_zero_rows(who, out, first, rows, pitch, row_bytes, device):
+    """Rows first .. rows-1 of out as ``render`` writes the rows past the frame: zero bytes."""
+    if isinstance(out, np.ndarray):
+        b = out.reshape(-1).view(np.uint8)
+        for r in range(first, rows):
+            b[r * pitch:r * pitch + row_bytes] = 0
+        return
+    if not hasattr(out, "numel"):
+        raise ValueError(f"{who}: a tile reaching past the frame needs out as a tensor (its padding rows are zeroed)")
+    import torch
+    b = out.view(torch.uint8).reshape(-1)
+    for r in range(first, rows):
+        b[r * pitch:r * pitch + row_bytes] = 0
+    torch.cuda.current_stream(device).synchronize()
+
+
+def _denoise_desc(color, pitch, hits, normals, width, rows, device, iterations, sigma_color, sigma_depth, normal_power,
+                  same_sphere):
+    d = L.OrtDenoiseDesc()
+    d.color, d.hits, d.normals = C.c_void_p(color), C.c_void_p(hits), C.c_void_p(normals)
+    d.color_pitch_bytes = 0 if pitch == 12 * width else int(pitch)
+    d.width, d.rows, d.on_device = int(width), int(rows), 1 if device else 0
+    d.iterations, d.normal_power = int(iterations), int(normal_power)
+    d.sigma_color, d.sigma_depth = float(sigma_color), float(sigma_depth)
+    d.flags = L.ORT_DENOISE_SAME_SPHERE if same_sphere else 0
+    return d
+
+
+def denoise_host(image, guides, *, iterations: int = 3, sigma_color: float = 0.0, sigma_depth: float = 0.0,
+                 normal_power: int = 5, same_sphere: bool = True, format: str = "rgb32f", row_pitch: int | None = None,
+                 out=None):
+    """TEST-ONLY: ``Renderer.denoise`` on the host CPU (ort_debug_denoise: denoise.inc's denoise_pixel,
+    the kernels' own per-pixel function).  image, guides, format, row_pitch, out: as there, numpy
+    arrays; out may be the image itself.  Returns out."""
+    lib = L.analysis_lib()
+    who = "denoise_host"
+    if not isinstance(image, np.ndarray):
+        raise ValueError(f"{who}: image must be a numpy array")
+    rows, width, pitch, color = _denoise_image(who, image, None)
+    hits, nrm, keep = _denoise_guides(who, guides, rows, width, None)
+    o, out = Renderer._output(None, who, None, Tile(0, width, 0, rows), out, format, row_pitch, "tile")
+    d = _denoise_desc(color, pitch, hits, nrm, width, rows, False, iterations, sigma_color, sigma_depth, normal_power,
+                      same_sphere)
+    L.acheck(lib.ort_debug_denoise(C.byref(d), C.byref(o)))
+    del keep
+    return out
