@@ -619,7 +619,9 @@ ORT_FN float fmin3(float a, float b, float c) { return fminf(fminf(a, b), c); }
 // (fma), and RN(q0 + r*y) = RN(n/a) (Markstein's theorem; no division is ever exactly a
 // midpoint).  Valid without underflow/overflow in r and q: |n| in [2^-60, 2^100] and
 // a in [2^-3, 2^3] (checked per ray by fast_path_ok); otherwise the IEEE division.
-// 2.56e9 random (n, a) pairs in those ranges were checked bitwise against n / a on the host.
+// 2.56e9 random (n, a) pairs in those ranges were checked bitwise against n / a on the host
+// (no artefact of that run is kept under profiles/; what the suite holds is tests/root_sets.py's
+// families against the oracle, tests/test_root_edges.py and tests/test_gpu_root_edges.py).
 // any_lane(p): p on any active lane of the wave (a wave-uniform branch: no exec-mask juggling
 // around a path that is almost never taken); p itself on the host.
 ORT_FN bool any_lane(bool p) {

@@ -63,7 +63,8 @@ def make_rays(ort, oracle, s, t, seed):
         a = next(a for a in range(3) if d[i, a] == 0.0)
         o[i, a] = t.node_min[rng.integers(0, t.n_nodes), a]
     parts.append(np.concatenate([o, d], axis=1))
-    # 4. scaled: directions of length 10^k, k in -3..3 (most leave the fast walk's range)
+    # 4. scaled: directions of length 10^k, k in -3..3 (most leave the fast walk's range; lengths
+    # that stay inside it, dot(d, d) over all of [1/8, 8] and at its ends: tests/root_sets.py)
     o, d = inside(300)
     parts.append(np.concatenate([o, d * 10.0 ** rng.integers(-3, 4, 300)[:, None]], axis=1))
     # 5. outside: beyond the box's far corner, pointing away
