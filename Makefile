@@ -12,7 +12,7 @@ HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -ffp-contract=off -fno-fast-ma
 HOST_SRCS := octree.cpp scene.cpp host_abi.cpp layout.cpp raytracer.cpp
 HOST_OBJS := $(addprefix $(OBJ)/,$(HOST_SRCS:.cpp=.o))
 HIP_OBJS := $(OBJ)/ort_kernel.o $(OBJ)/gpu_build.o $(OBJ)/group.o
-HDRS := $(wildcard $(SRC)/*.h) $(SRC)/prebuilt_scene.inc $(SRC)/ray_query.inc $(SRC)/accum.inc $(SRC)/camera_query.inc $(SRC)/ray_modes.inc $(SRC)/radiance_query.inc $(SRC)/denoise.inc $(SRC)/host_emulation.inc include/ort.h include/ort_math.h
+HDRS := $(wildcard $(SRC)/*.h) $(wildcard $(SRC)/*.inc) include/ort.h include/ort_math.h
 
 # The analysis library (test/analysis surface: ort_debug_* host emulation and walk statistics,
 # ORT_OPT_DEBUG_FLAGS) -- the same sources with -DORT_ANALYSIS=1; the CPU suite and tools/
@@ -55,31 +55,14 @@ $(LIB): $(HOST_OBJS) $(HIP_OBJS)
 	@mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -ldl -Wl,-soname,libort.so
 
-examples: build/ort_main build/stats_row build/trace_rays build/progressive build/pick build/visibility build/radiance_probe build/denoise
+EXAMPLES := stats_row trace_rays progressive pick visibility radiance_probe denoise
+examples: build/ort_main $(addprefix build/,$(EXAMPLES))
 
-build/denoise: tests/cpp/denoise.cpp $(LIB) $(HDRS)
-	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ tests/cpp/denoise.cpp -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
-
-build/radiance_probe: tests/cpp/radiance_probe.cpp $(LIB) $(HDRS)
-	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ tests/cpp/radiance_probe.cpp -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
-
-build/visibility: tests/cpp/visibility.cpp $(LIB) $(HDRS)
-	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ tests/cpp/visibility.cpp -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
-
-build/pick: tests/cpp/pick.cpp $(LIB) $(HDRS)
-	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ tests/cpp/pick.cpp -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
-
-build/progressive: tests/cpp/progressive.cpp $(LIB) $(HDRS)
-	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ tests/cpp/progressive.cpp -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
-
-build/trace_rays: tests/cpp/trace_rays.cpp $(LIB) $(HDRS)
-	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ tests/cpp/trace_rays.cpp -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
-
-build/stats_row: tests/cpp/stats_row.cpp $(LIB) $(HDRS)
-	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ tests/cpp/stats_row.cpp -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
+$(addprefix build/,$(EXAMPLES)): build/%: tests/cpp/%.cpp $(LIB) $(HDRS)
+	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ $< -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
 
 build/ort_main: examples/main.cpp $(LIB) $(HDRS)
-	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ examples/main.cpp -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
+	$(CXX) -O2 -std=c++17 -I$(SRC) -o $@ $< -L$(dir $(LIB)) -lort -Wl,-rpath,'$$ORIGIN/../$(dir $(LIB))'
 
 oracle:
 	$(MAKE) -C oracle all
@@ -97,14 +80,13 @@ SAN_HOST := $(addprefix $(SANOBJ)/,$(HOST_SRCS:.cpp=.o))
 SAN_HIP := $(SANOBJ)/ort_kernel.o $(SANOBJ)/gpu_build.o $(SANOBJ)/group.o
 HIP_SAN := $(foreach f,address undefined,-Xarch_host -fsanitize=$(f)) -Xarch_host -fno-sanitize-recover=undefined
 
-san: build/san/san_check build/san/san_query build/san/san_camera build/san/san_query_modes build/san/san_radiance build/san/san_denoise
-	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/san_check
-	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/san_query
-	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/san_camera
-	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/san_query_modes
-	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/san_radiance
-	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/san_denoise
+SAN_PROGS := san_check san_query san_camera san_query_modes san_radiance san_denoise
+define RUN_SAN
+ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/$(1)
 
+endef
+san: $(addprefix build/san/,$(SAN_PROGS))
+	$(foreach p,$(SAN_PROGS),$(call RUN_SAN,$(p)))
 $(SANOBJ)/%.o: $(SRC)/%.cpp $(HDRS)
 	@mkdir -p $(SANOBJ)
 	$(CLANGXX) $(SAN) -std=c++17 -ffp-contract=off -fno-fast-math -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -c $< -o $@
@@ -121,47 +103,16 @@ $(SANOBJ)/san_check.o: tests/cpp/san_check.cpp $(HDRS) oracle/ort_oracle.h
 	@mkdir -p $(SANOBJ)
 	$(CLANGXX) $(SAN) -std=c++17 -I$(SRC) -Ioracle -c $< -o $@
 
-# the ray queries' host code (ort_debug_query_rays: render_core.h query_ray) under the same sanitizers
-$(SANOBJ)/san_query.o: tests/cpp/san_query.cpp $(HDRS)
+# the host code of the ray queries (ort_debug_query_rays: render_core.h query_ray), the camera queries
+# (ort_debug_camera_query: camera_query.inc camera_query_ray), the query modes (ort_debug_query_rays_ex:
+# render_core.h query_ray_mode), the radiance queries (ort_debug_radiance_rays: radiance_query.inc
+# radiance_chain) and the denoiser (ort_debug_denoise: denoise.inc denoise_pixel) under the same sanitizers
+$(SANOBJ)/san_%.o: tests/cpp/san_%.cpp $(HDRS)
 	@mkdir -p $(SANOBJ)
 	$(CLANGXX) $(SAN) -std=c++17 -I$(SRC) -c $< -o $@
 
-# the camera queries' host code (ort_debug_camera_query: camera_query.inc camera_query_ray) likewise
-$(SANOBJ)/san_camera.o: tests/cpp/san_camera.cpp $(HDRS)
-	@mkdir -p $(SANOBJ)
-	$(CLANGXX) $(SAN) -std=c++17 -I$(SRC) -c $< -o $@
-
-# the query modes' host code (ort_debug_query_rays_ex: render_core.h query_ray_mode) likewise
-$(SANOBJ)/san_query_modes.o: tests/cpp/san_query_modes.cpp $(HDRS)
-	@mkdir -p $(SANOBJ)
-	$(CLANGXX) $(SAN) -std=c++17 -I$(SRC) -c $< -o $@
-
-# the radiance queries' host code (ort_debug_radiance_rays: radiance_query.inc radiance_chain) likewise
-$(SANOBJ)/san_radiance.o: tests/cpp/san_radiance.cpp $(HDRS)
-	@mkdir -p $(SANOBJ)
-	$(CLANGXX) $(SAN) -std=c++17 -I$(SRC) -c $< -o $@
-
-# the denoiser's host code (ort_debug_denoise: denoise.inc denoise_pixel) likewise
-$(SANOBJ)/san_denoise.o: tests/cpp/san_denoise.cpp $(HDRS)
-	@mkdir -p $(SANOBJ)
-	$(CLANGXX) $(SAN) -std=c++17 -I$(SRC) -c $< -o $@
-
-build/san/san_denoise: $(SANOBJ)/san_denoise.o $(SAN_HOST) $(SAN_HIP)
-	$(HIPCC) --offload-arch=$(ARCH) $(SAN) -o $@ $^ -ldl
-
-build/san/san_radiance: $(SANOBJ)/san_radiance.o $(SAN_HOST) $(SAN_HIP)
-	$(HIPCC) --offload-arch=$(ARCH) $(SAN) -o $@ $^ -ldl
-
-build/san/san_query_modes: $(SANOBJ)/san_query_modes.o $(SAN_HOST) $(SAN_HIP)
-	$(HIPCC) --offload-arch=$(ARCH) $(SAN) -o $@ $^ -ldl
-
-build/san/san_camera: $(SANOBJ)/san_camera.o $(SAN_HOST) $(SAN_HIP)
-	$(HIPCC) --offload-arch=$(ARCH) $(SAN) -o $@ $^ -ldl
-
-build/san/san_query: $(SANOBJ)/san_query.o $(SAN_HOST) $(SAN_HIP)
-	$(HIPCC) --offload-arch=$(ARCH) $(SAN) -o $@ $^ -ldl
-
-build/san/san_check: $(SANOBJ)/san_check.o $(SAN_HOST) $(SAN_HIP) $(SANOBJ)/ort_oracle.o
+build/san/san_check: $(SANOBJ)/ort_oracle.o
+$(addprefix build/san/,$(SAN_PROGS)): build/san/%: $(SANOBJ)/%.o $(SAN_HOST) $(SAN_HIP)
 	$(HIPCC) --offload-arch=$(ARCH) $(SAN) -o $@ $^ -ldl
 
 ref:

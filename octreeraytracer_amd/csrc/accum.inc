@@ -44,9 +44,9 @@ hipError_t launch_accum_paths(int device, int mode, bool deep, bool lds_scene, s
 // refusal: what the whole-pixel kernel does not exist for.
 int accum_mode(ort_ctx* ctx, const ort_params* p, const char* call, int& mode) {
     const std::string who = std::string(call) + ": ";
-    if (!ctx->has_scene) return fail(ctx, ORT_ERR_NO_SCENE, who + "no scene uploaded");
-    mode = (p->use_octree == 1) ? (ctx->layout == ORT_LAYOUT_COMPACT ? 0 : 1) : 2;
-    if (mode != 2 && ctx->n_nodes <= 0) return fail(ctx, ORT_ERR_NO_SCENE, who + "scene has no octree");
+    if (!ctx->scene.has_scene) return fail(ctx, ORT_ERR_NO_SCENE, who + "no scene uploaded");
+    mode = (p->use_octree == 1) ? (ctx->scene.layout == ORT_LAYOUT_COMPACT ? 0 : 1) : 2;
+    if (mode != 2 && ctx->scene.n_nodes <= 0) return fail(ctx, ORT_ERR_NO_SCENE, who + "scene has no octree");
     if (mode == 1)
         return fail(ctx, ORT_ERR_UNSUPPORTED, who + "use_octree = 1 on the explicit layout (passes take the whole-pixel "
                                                     "kernel: compact layout or brute force)");
@@ -74,11 +74,11 @@ int accum_begin_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, ort_a
     acc->t = *t;
     acc->mode = mode;
     acc->blocks = blocks;
-    acc->scene_gen = ctx->scene_gen;
+    acc->scene_gen = ctx->scene.scene_gen;
     const size_t slots = (size_t)blocks * kBlock;
     hipError_t e = hipSuccess;
     if ((rc = ensure(ctx, acc->state, std::max<size_t>(20 * slots, 16))) || (rc = ensure(ctx, acc->sync, 64)) ||
-        (e = hipEventCreate(&acc->ev0)) != hipSuccess || (e = hipEventCreate(&acc->ev1)) != hipSuccess) {
+        (e = acc->ev.create()) != hipSuccess) {
         if (!rc) rc = hip_fail(ctx, e, "ort_accum_begin: events");
         free_accum(acc);
         return rc;
@@ -101,7 +101,7 @@ int accum_restart_impl(ort_ctx* ctx, ort_accum* acc, const ort_params* p) {
     acc->p = *p;
     acc->mode = mode;
     acc->done = 0;
-    acc->scene_gen = ctx->scene_gen;
+    acc->scene_gen = ctx->scene.scene_gen;
     return ORT_OK;
 }
 
@@ -115,7 +115,7 @@ int accum_render_impl(ort_ctx* ctx, ort_accum* acc, int n_samples, const ort_out
         if (!bad_out.empty()) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_accum_render: " + bad_out);
         if (!o->data && pix > 0) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_accum_render: null output data");
     }
-    if (acc->scene_gen != ctx->scene_gen || !ctx->has_scene)
+    if (acc->scene_gen != ctx->scene.scene_gen || !ctx->scene.has_scene)
         return fail(ctx, ORT_ERR_NO_SCENE,
                     "ort_accum_render: the scene changed since the accumulation was begun (ort_accum_restart starts "
                     "it again on the new scene)");
@@ -152,12 +152,12 @@ int accum_render_impl(ort_ctx* ctx, ort_accum* acc, int n_samples, const ort_out
     a.fx_col = (float*)((char*)acc->state.p + sizeof(float2) * slots);
     a.sample = s0;
     a.sp_chunk = s1;
-    HIPCHK(ctx, hipEventRecord(acc->ev0, s));
+    HIPCHK(ctx, acc->ev.begin(s));
     if (s1 > s0) {
         HIPCHK(ctx, hipMemsetAsync(acc->sync.p, 0, 64, s));
         bool lds_scene;
         const size_t lds = pixel_paths_lds(ctx, acc->mode, a, lds_scene);
-        const hipError_t e = launch_accum_paths(ctx->device, acc->mode, ctx->depth > 8, lds_scene, lds, acc->blocks, a, s);
+        const hipError_t e = launch_accum_paths(ctx->device, acc->mode, ctx->scene.depth > 8, lds_scene, lds, acc->blocks, a, s);
         if (e != hipSuccess) return hip_fail(ctx, e, "ort_pixel_paths (accumulation pass) launch");
         acc->done = s1;
     } else if (o) {  // finished before the call: the frame again, from the stored sums
@@ -165,8 +165,7 @@ int accum_render_impl(ort_ctx* ctx, ort_accum* acc, int n_samples, const ort_out
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(ctx, e, "ort_accum_resolve launch");
     }
-    HIPCHK(ctx, hipEventRecord(acc->ev1, s));
-    acc->timed = true;
+    HIPCHK(ctx, acc->ev.end(s));
     if (o) return finish_output(ctx, o, dout, t, pitch, stream, s);
     if (!stream) HIPCHK(ctx, hipStreamSynchronize(s));
     return ORT_OK;
@@ -209,9 +208,8 @@ int ort_accum_last_pass_ms(ort_ctx* ctx, ort_accum* accum, float* ms) {
     if (!ctx || !accum || !ms) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_accum_last_pass_ms: null argument");
     if (!accum_known(ctx, accum))
         return fail(ctx, ORT_ERR_INVALID_ARG, "ort_accum_last_pass_ms: not an accumulation of this context");
-    if (!accum->timed) return fail(ctx, ORT_ERR_NO_SCENE, "no pass launched yet");
-    HIPCHK(ctx, hipEventSynchronize(accum->ev1));
-    HIPCHK(ctx, hipEventElapsedTime(ms, accum->ev0, accum->ev1));
+    if (!accum->ev.timed) return fail(ctx, ORT_ERR_NO_SCENE, "no pass launched yet");
+    HIPCHK(ctx, accum->ev.elapsed(ms));
     return ORT_OK;
 }
 
@@ -220,7 +218,7 @@ int ort_accum_free(ort_ctx* ctx, ort_accum* accum) {
     if (!accum) return ORT_OK;
     if (!accum_known(ctx, accum)) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_accum_free: not an accumulation of this context");
     (void)hipSetDevice(ctx->device);
-    if (accum->timed) (void)hipEventSynchronize(accum->ev1);  // its last pass has left the state
+    if (accum->ev.timed) (void)hipEventSynchronize(accum->ev.ev1);  // its last pass has left the state
     ctx->accums.erase(std::find(ctx->accums.begin(), ctx->accums.end(), accum));
     free_accum(accum);
     return ORT_OK;

@@ -256,14 +256,13 @@ int denoise_impl(ort_ctx* ctx, const ort_denoise_desc* d, const ort_output* o, v
     if (host && ((rc = ensure(ctx, ds.in_color, 12 * n)) || (rc = ensure(ctx, ds.in_hits, 8 * n)) ||
                  (rc = ensure(ctx, ds.in_normals, 12 * n)) || (rc = ensure(ctx, ds.out, out_row * rows))))
         return rc;
-    if (!ds.ev0) HIPCHK(ctx, hipEventCreate(&ds.ev0));
-    if (!ds.ev1) HIPCHK(ctx, hipEventCreate(&ds.ev1));
+    HIPCHK(ctx, ds.ev.create());
     if (host) {  // the inputs, tight on the device
         HIPCHK(ctx, hipMemcpy2DAsync(ds.in_color.p, in_row, d->color, in_pitch, in_row, rows, hipMemcpyHostToDevice, s));
         HIPCHK(ctx, hipMemcpyAsync(ds.in_hits.p, d->hits, 8 * n, hipMemcpyHostToDevice, s));
         HIPCHK(ctx, hipMemcpyAsync(ds.in_normals.p, d->normals, 12 * n, hipMemcpyHostToDevice, s));
     }
-    HIPCHK(ctx, hipEventRecord(ds.ev0, s));
+    HIPCHK(ctx, ds.ev.begin(s));
     DenoisePackArgs pa;
     std::memset(&pa, 0, sizeof(pa));
     pa.color = host ? (const unsigned char*)ds.in_color.p : (const unsigned char*)d->color;
@@ -296,8 +295,7 @@ int denoise_impl(ort_ctx* ctx, const ort_denoise_desc* d, const ort_output* o, v
         const int fmt = !last ? 0 : (o->format == ORT_FORMAT_RGBA8 ? 2 : 1);
         if ((e = launch_denoise_iter(fmt, blocks, s, a)) != hipSuccess) return hip_fail(ctx, e, "ort_denoise_iter launch");
     }
-    HIPCHK(ctx, hipEventRecord(ds.ev1, s));
-    ds.timed = true;
+    HIPCHK(ctx, ds.ev.end(s));
     if (host) {
         HIPCHK(ctx, hipMemcpy2DAsync(o->data, out_pitch, ds.out.p, out_row, out_row, rows, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipStreamSynchronize(s));
@@ -322,10 +320,9 @@ int ort_denoise(ort_ctx* ctx, const ort_denoise_desc* d, const ort_output* outpu
 
 int ort_last_denoise_ms(ort_ctx* ctx, float* ms) {
     if (!ctx || !ms) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_last_denoise_ms: null argument");
-    if (!ctx->denoise.timed) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_last_denoise_ms: no denoise launched yet");
+    if (!ctx->denoise.ev.timed) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_last_denoise_ms: no denoise launched yet");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipEventSynchronize(ctx->denoise.ev1));
-    HIPCHK(ctx, hipEventElapsedTime(ms, ctx->denoise.ev0, ctx->denoise.ev1));
+    HIPCHK(ctx, ctx->denoise.ev.elapsed(ms));
     return ORT_OK;
 }
 

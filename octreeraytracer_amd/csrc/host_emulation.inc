@@ -623,12 +623,12 @@ int ort_debug_leaf16(const float* cr, int32_t n_spheres, const float* node_min, 
 // returns their number through n.
 int ort_debug_ctx_leaf16(ort_ctx* ctx, uint32_t* out, int64_t cap, int64_t* n) {
     if (!ctx || !n) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_debug_ctx_leaf16: null argument");
-    *n = ctx->leaf16.p ? (int64_t)(ctx->leaf16.bytes / 16) : 0;
+    *n = ctx->scene.leaf16.p ? (int64_t)(ctx->scene.leaf16.bytes / 16) : 0;
     if (!out || *n == 0) return ORT_OK;
     if (cap < *n) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_debug_ctx_leaf16: out too small");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(out, ctx->leaf16.p, ctx->leaf16.bytes, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(out, ctx->scene.leaf16.p, ctx->scene.leaf16.bytes, hipMemcpyDeviceToHost));
     return ORT_OK;
 }
 

@@ -15,6 +15,8 @@
 // The walk keeps one frame per tree level in LDS (columns indexed by lane: conflict-free),
 // per-level child masks in registers, and the tree's split-plane table in LDS
 // (3 x (2^D+1) floats, loaded once per workgroup).
+// This file holds the kernels; the host half of the translation unit is the host_*.inc files
+// included after them, followed by the queries', accumulation's and denoiser's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1885,321 +1887,11 @@ __global__ void __launch_bounds__(256) ort_sample_moved(PipeArgs A, int* count) 
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(count, __popcll(m));
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
-// The queries' own state (ort_trace_rays, ort_trace_rays_ex, ort_trace_camera: ray_query.inc), none of
-// the per-frame pipeline's: the staging of host arrays (grow-only; trange: ort_trace_rays_ex's
-// intervals; states, radiance: ort_trace_radiance's), the defer list and the {deferred count, cursor} counters, ORT_QUERY_SORT's keys and
-// lists, the timing events of the last query.
-struct QueryState {
-    DevBuf rays, hits, normals, trange, states, radiance;
-    DevBuf defer, sync;
-    DevBuf keys, keys2, vals, list, temp;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-};
-
-// The denoiser's own state (ort_denoise: denoise.inc), none of the queries' or the pipeline's: the
-// staging of host arrays and of a host output (grow-only), the packed guide records, the two
-// colour buffers the iterations ping-pong between, the timing events of the last denoise.
-struct DenoiseState {
-    DevBuf in_color, in_hits, in_normals, out;
-    DevBuf guide, col_a, col_b;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-};
-
-}  // namespace
-
-#ifndef ORT_HEAVY_STEPS
-#define ORT_HEAVY_STEPS 64  // ORT_OPT_HEAVY_FIRST default: classes >= 256, >= 128, >= 64 steps
-#endif
-// Camera-ray defaults, measured with tools/ab_stream.py: a raised issue priority
-// for waves holding a >= 150-step walk (C3 1/8 band +15 %, full frame +-0); split walks of the
-// >= 200-step rays on tiles of at most 2^21 pixels (C3 1/8 band +26 %, 1/4 band +21 %, 1/2 band
-// -2 %, full frame -2 %) and tile pairs on the larger ones (full frame +1.2 %, 1/2 band +0.8 %;
-// 1/4 band: split +21 % > pairs +16 %; 1/8 band: pairs with split -22 %).
-constexpr int kHeavyPrioSteps = 150;
-constexpr int kSplitAutoSteps = 200;
-constexpr long long kSplitAutoPixels = 1ll << 21;
-constexpr long long kPairsAutoPixels = kSplitAutoPixels + 1;
-// ORT_OPT_XCD_SWIZZLE -1 (auto): raster order (0) for the per-tile kernel on tiles of at most
-// this many pixels, runs (2) otherwise.  A C3 1/8 band (1 M pixels, ~2 generations of
-// workgroups) at one frame in flight: 0.307 -> 0.298 ms with raster order (its heavy region
-// spread over all 8 XCDs instead of runs of 16 tiles on one); a 1/4 band 0.492 vs 0.505 and
-// tile pairs (frames in flight) 0.224 vs 0.242 ms the other way (profiles/r05_band_swizzle.log)
-constexpr long long kRasterAutoPixels = 3ll << 19;
-struct ort_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t ev0_last = nullptr;  // the last frame's start: ev0, or its first trace-timing event
-    static constexpr int kRing = 64;           // trace-kernel timing of the last 64 frames
-    static constexpr int kSeg = 16;            // ... of their first 16 trace launches each
-    hipEvent_t tr0[kRing][kSeg] = {}, tr1[kRing][kSeg] = {};  // segment 0 created up front, others lazily
-    int tseg[kRing] = {};                      // trace launches timed in each frame slot
-    long long frames = 0;                      // frames whose first trace kernel was timed
-    bool timed = false;
-    std::string err;
-    int force_layout = -1;
-    int exact_only = 0;
-    int pixel_paths = -1;  // ORT_OPT_PIXEL_PATHS: -1 auto (use_pixel_paths), 0 off, 1 on where it applies
-    int pixel_lds_scene = 1;  // ORT_OPT_PIXEL_LDS_SCENE: small scenes in LDS for whole-pixel paths
-    int pixel_heavy_first = -1;  // ORT_OPT_PIXEL_HEAVY_FIRST: -1 auto (2+ samples), 0 off, 1 on
-    int refill = 16;  // ORT_OPT_REFILL: C5 (64-item chunks) 16 > 12 (-0.6 %) > 8 (-1.2 %); tools/ab_stream.py
-    int persistent = 2;  // ORT_OPT_PERSISTENT: 0 off, 2 bounce >= 1 traces (default)
-#if ORT_ANALYSIS
-    void* wclock = nullptr;  // ort_debug_wave_clock (ORT_PERSIST_CLOCK analysis builds)
-    long long wclock_n = 0;
-#endif
-    int xcd_swizzle = -1;  // ORT_OPT_XCD_SWIZZLE: workgroup -> tile order (block_tile); -1 auto
-    int kid_skip = 1;     // ORT_OPT_KID_SKIP: rejected-sphere skip of one-sphere leaf children (2: without nk)
-    // ORT_OPT_SORT_PATHS: order of the alive paths between bounces.  2 (default): the list the
-    // shade kernel appended, radix-sorted by the coherence key after reading its length back --
-    // C5 bounce traces 33.8 -> 31.2 ms, frame 55.5 -> 54.9 ms (A/B).  1 (every slot's key sorted,
-    // dead ones last) costs as much as it saves; coarser orders lose: octant only or 12-18 key
-    // bits ~ slot order, octant + direction bits and 16-bit atomic buckets slower than slot
-    // order, a block-local sort of 4096-entry runs (rocprim block_radix_sort) 55.4 ms.
-    int sort_paths = 2;
-    // The list sort without a host wait (sortListBounded): its size is a host-side bound, the
-    // list's length from the same bounce of an earlier frame (read back asynchronously into
-    // pinned memory: alive_host[sample * bounces + bounce]) plus a margin; a longer list goes
-    // on unsorted (same pixels).  hint_sig: the frame shape the hints belong to.  The hints live
-    // in one of kHintBanks banks: a new shape takes a bank that no copy is still headed for (the
-    // event after the bank's last copy has completed), so a copy of the old shape's frames
-    // still in flight cannot land in the new shape's hints.
-    static constexpr int kHints = 64;
-    static constexpr int kHintBanks = 4;
-    int* alive_host = nullptr;         // kHintBanks x kHints
-    int hint_bank = 0;
-    hipEvent_t hint_ev[kHintBanks] = {};
-    bool hint_ev_used[kHintBanks] = {};
-    unsigned long long hint_sig = 0;
-    int sort_bound = 0;  // ORT_OPT_SORT_BOUND (testing): > 0 forces this bound
-    // ORT_OPT_COST_ORDER (cost_order_slot): per slot the walk steps of its last camera ray,
-    // cleared when the frame shape or scene changes (cost_sig)
-    int cost_order = 1;
-    DevBuf pcost;
-    // whole-pixel paths, heavy blocks first: two {kPixelClasses segments of block lists} buffers
-    // and their counts, the blocks' cost accumulators, the parity of the next frame's write
-    // buffer, and the shape the read buffer's lists belong to (0: none)
-    DevBuf pplist, ppcnt, ppcost;
-    // samples in parallel (ORT_OPT_PIXEL_SPECULATE): the two per-chunk end-state buffers (spst,
-    // which one is last frame's: sp_par), the samples' radiance, the fixup list and its length,
-    // and the shape the recorded states belong to (0: none)
-    DevBuf spst, spcol, spfix, spfixn;
-    int sp_par = 0;
-    unsigned long long sp_sig = 0;
-    // (the pixels a frame found moved, and whether the next one speculates: spfixn, PipeArgs::sp_ctl)
-    // ORT_OPT_PIXEL_SPECULATE auto (-1): per shape, a whole-chain frame's time (frame slot
-    // sp_tslot[0]) against a speculating frame's (sp_tslot[1]) decides sp_use
-    // 0 fresh, 1 first frame done, 2 first speculating frame done (warm-up of both), 3 whole-chain
-    // frame measured, 4 speculating frame measured, 5 decided
-    int sp_tune = 0;
-    int sp_tslot[2] = {0, 0};
-    long long sp_tframe = 0;  // ctx->frames when the whole-chain side was measured
-    bool sp_use = true;
-
-    int pixel_spec = -1;  // ORT_OPT_PIXEL_SPECULATE: -1 auto, 0 off, 1 on
-    int pp_par = 0;
-    unsigned long long pp_sig = 0;
-    unsigned long long cost_sig = 0;
-    // ORT_OPT_HEAVY_FIRST: threshold in walk steps (0 off); bcost holds, per bounce >= 1 of the
-    // first kCostBounces of a frame, every slot's last walk steps (cleared with cost_sig)
-    static constexpr int kCostBounces = 8;
-    int heavy_first = ORT_HEAVY_STEPS;
-    int heavy_prio = kHeavyPrioSteps;  // ORT_OPT_HEAVY_PRIO (steps; 0 off)
-    ort::KCamera prio_cam{};           // the camera of this context's last frame (heavy priority: static only)
-    // ORT_OPT_TILE_PAIRS: camera-ray workgroups of two tiles (cost_order_pair); -1 = auto (tiles
-    // of at least kPairsAutoPixels)
-    int tile_pairs = -1;
-    // ORT_OPT_SPLIT_HEAVY (steps; 0 off; -1 = auto: kSplitAutoSteps on tiles of at most
-    // kSplitAutoPixels) / ORT_OPT_SPLIT_LEVEL (0: auto): the heavy camera rays of a 1-sample
-    // frame walked by ort_trace_split on aux_stream (k_heavy_scan lists them)
-    int split_steps = -1;
-    int split_level = 0;
-    static constexpr int kSplitCap = 4096;  // heavy rays listed per frame at most
-    hipStream_t aux_stream = nullptr;
-    hipEvent_t ev_scan = nullptr, ev_split = nullptr, ev_pre = nullptr;
-    // the next frame's heavy list is listed by a split frame's exact kernel (pcost final by then)
-    // instead of by a scan opening the next frame: pre_ok when the list in hbits/hlist/hcnt[hpar]
-    // is that of a frame of shape pre_sig and threshold pre_steps
-    bool pre_ok = false;
-    unsigned long long pre_sig = 0;
-    int pre_steps = 0, hpar = 0;
-    DevBuf hcnt;  // two {heavy count, split cursor} pairs (16 ints): ort_trace_split zeroes the other
-    DevBuf hbits, hlist;
-    DevBuf bcost;
-    unsigned long long bcost_sig = 0;
-    float root_lo[3] = {0, 0, 0}, root_hi[3] = {0, 0, 0};  // root box (coherence-sort key)
-    ort::GpuTree tree;  // reference-layout tree of the last ort_build_scene(keep_tree)
-    float build_ms = 0.0f;
-    bool has_scene = false;
-    int layout = ORT_LAYOUT_EXPLICIT;
-    int depth = 0;
-    bool ordered = true;  // compact layout: fast walk allowed (CompactLayout::ordered)
-    int32_t n_spheres = 0, n_nodes = 0;
-    int64_t n_indices = 0;
-    DevBuf sph_cr, sph_ma, sph_fr;
-    DevBuf node, leaf_sph, leaf_idx, planes, kid;  // compact
-    DevBuf nk;                                   // ... node records and kid entries interleaved (build_nk)
-    DevBuf leaf16;                               // ... depth <= 8: the 16-byte leaf records (build_leaf16)
-    DevBuf lds_img;                              // compact: the workgroup LDS image (k_lds_image)
-    DevBuf lds_rev;                              // ... depth 9-10: the reversed-table image (persistent kernel)
-    DevBuf nodeA, nodeB, cnt, indices;           // explicit
-    DevBuf scratch_out, counters;
-    // wavefront pipeline state, sized for the largest tile rendered so far
-    DevBuf hit, defer_list, defer_count, po, pd, pc, prng, pcol;
-    int sync_set = 0;      // defer_count's counter set of the next trace launch (render_impl)
-    int debug_flags = 0;   // ORT_OPT_DEBUG_FLAGS (A/B of the per-frame stream structure only)
-    int launch_times = 1;  // ORT_OPT_LAUNCH_TIMES: per-launch trace-timing events
-    bool sync_ok = false;  // both sets zero except the one the last exact kernel left to zero
-    DevBuf qlist, qlist2, qcount, qtemp;  // bounce >= 1 path compaction (two lists: read one, append the other)
-    DevBuf skeys, skeys2, svals;  // coherence sort
-    DevBuf key_spread;            // its origin-code tables for the scene's root box (path_key.h)
-    float spread_box[6] = {0, 0, 0, 0, 0, 0};  // the root box key_spread was built for
-    QueryState query;  // ray, camera and mode queries (ray_query.inc)
-    DenoiseState denoise;  // ort_denoise (denoise.inc)
-    // accumulations (ort_accum_*, accum.inc): the live ones, each with its own state, counters and
-    // events (ort_destroy frees what is left), and the scene's generation: free_scene advances
-    // it, and an accumulation begun or restarted under another one is stale
-    std::vector<ort_accum*> accums;
-    unsigned long long scene_gen = 0;
-};
-
-// A frame's samples accumulated over several passes (include/ort.h): the frame and tile it was
-// begun with, the samples done, and per path slot (tile-block order, as PipeArgs::total) the RNG
-// state (float2) followed by the colour sum's three planes -- 20 bytes a slot, each array read and
-// written by consecutive lanes for consecutive slots.
-struct ort_accum {
-    ort_ctx* ctx = nullptr;
-    ort_params p{};
-    ort_tile t{};
-    int mode = 0;          // 0 the compact layout's walk, 2 brute force
-    int done = 0;
-    long long blocks = 0;  // 16x16 tiles
-    unsigned long long scene_gen = 0;
-    DevBuf state;          // float2[slots] | float[3][slots]
-    DevBuf sync;           // the launch's cursor and done count (16 ints, zeroed before every pass)
-    DevBuf stage;          // host output: the tight picture on the device (allocated by the first such pass)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-};
-
-namespace {
-
-int fail(ort_ctx* ctx, int code, const std::string& msg) {
-    if (ctx) ctx->err = msg;
-    ort::set_thread_error(msg);
-    return code;
-}
-
-int hip_fail(ort_ctx* ctx, hipError_t e, const char* what) {
-    return fail(ctx, e == hipErrorOutOfMemory ? ORT_ERR_OUT_OF_MEMORY : ORT_ERR_HIP,
-                std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define HIPCHK(ctx, expr)                                  \
-    do {                                                   \
-        hipError_t _e = (expr);                            \
-        if (_e != hipSuccess) return hip_fail(ctx, _e, #expr); \
-    } while (0)
-
-void free_buf(DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-}
-
-void free_query(QueryState& q) {
-    for (DevBuf* b : {&q.rays, &q.hits, &q.normals, &q.trange, &q.states, &q.radiance, &q.defer, &q.sync, &q.keys, &q.keys2, &q.vals, &q.list, &q.temp})
-        free_buf(*b);
-    if (q.ev0) (void)hipEventDestroy(q.ev0);
-    if (q.ev1) (void)hipEventDestroy(q.ev1);
-    q = QueryState{};
-}
-
-void free_denoise(DenoiseState& d) {
-    for (DevBuf* b : {&d.in_color, &d.in_hits, &d.in_normals, &d.out, &d.guide, &d.col_a, &d.col_b}) free_buf(*b);
-    if (d.ev0) (void)hipEventDestroy(d.ev0);
-    if (d.ev1) (void)hipEventDestroy(d.ev1);
-    d = DenoiseState{};
-}
-
-// The scene's device buffers (C: ort_ctx or const ort_ctx): the one list free_scene frees and
-// ort_scene_get_info sums.
-template <class C, class F>
-void each_scene_buffer(C& c, F f) {
-    for (auto* b : {&c.sph_cr, &c.sph_ma, &c.sph_fr, &c.node, &c.kid, &c.nk, &c.leaf16, &c.leaf_sph, &c.leaf_idx, &c.planes,
-                    &c.lds_img, &c.lds_rev, &c.nodeA, &c.nodeB, &c.cnt, &c.indices})
-        f(*b);
-}
-
-void free_scene(ort_ctx* c) {
-    each_scene_buffer(*c, [](DevBuf& b) { free_buf(b); });
-    ort::freeGpuTree(c->tree);
-    c->has_scene = false;
-    c->scene_gen += 1;  // the accumulations begun on this scene are stale (accum.inc)
-}
-
-// An accumulation's device memory and events, and the object (its context's list is the caller's).
-void free_accum(ort_accum* a) {
-    free_buf(a->state);
-    free_buf(a->sync);
-    free_buf(a->stage);
-    if (a->ev0) (void)hipEventDestroy(a->ev0);
-    if (a->ev1) (void)hipEventDestroy(a->ev1);
-    delete a;
-}
-
-int upload(ort_ctx* ctx, DevBuf& b, const void* src, size_t bytes) {
-    free_buf(b);
-    if (bytes == 0) bytes = 16;  // keep a valid pointer for empty arrays
-    HIPCHK(ctx, hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    if (src) HIPCHK(ctx, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return ORT_OK;
-}
-
-// The compact layout's workgroup LDS image (plane tables | rank LUT) from ctx->planes.
-int build_lds_image(ort_ctx* ctx) {
-    for (int rev = 0; rev < 2; ++rev) {
-        if (rev && !(kRevBounce && ctx->depth > 8)) break;
-        DevBuf& img = rev ? ctx->lds_rev : ctx->lds_img;
-        const size_t bytes = (size_t)ort::lds_layout(ctx->depth, rev || ort::fast_rev_planes(ctx->depth)).frames;
-        int rc;
-        if ((rc = upload(ctx, img, nullptr, bytes))) return rc;
-        hipLaunchKernelGGL(k_lds_image, dim3(1), dim3(kBlock), 0, ctx->stream, (const float*)ctx->planes.p, ctx->depth,
-                           rev != 0, (unsigned char*)img.p);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    return ORT_OK;
-}
-
 __global__ void __launch_bounds__(kBlock) k_interleave_nk(const uint2* node, const uint2* kid, uint4* nk, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const uint2 a = node[i], b = kid[i];
     nk[i] = make_uint4(a.x, a.y, b.x, b.y);
-}
-
-// The walks that use the rejected-sphere skip load a node's record and kid entry together
-// (fetch_rec): one 16-byte load, one cache line per record instead of one in each array.
-// Built when both arrays are there and 16 bytes per node stay under the buffer loads' 4 GiB.
-int build_nk(ort_ctx* ctx) {
-    free_buf(ctx->nk);
-    const int64_t n = (int64_t)(ctx->node.bytes / 8);
-    if (!ORT_NODE_KID || !ctx->kid.p || ctx->kid.bytes < ctx->node.bytes || n == 0 || 16 * n >= (int64_t)UINT32_MAX)
-        return ORT_OK;
-    int rc;
-    if ((rc = upload(ctx, ctx->nk, nullptr, 16 * (size_t)n))) return rc;
-    hipLaunchKernelGGL(k_interleave_nk, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                       (const uint2*)ctx->node.p, (const uint2*)ctx->kid.p, (uint4*)ctx->nk.p, n);
-    HIPCHK(ctx, hipGetLastError());
-    return ORT_OK;
 }
 
 // KScene::leaf16 from node[] and leaf_sph[] (n_ent entries), record by record through
@@ -2213,1522 +1905,17 @@ __global__ void __launch_bounds__(kBlock) k_leaf16(const uint2* node, const uint
     leaf16[i] = ort::leaf16_record(rec, sp);
 }
 
-// The depth <= 8 camera walk reads its leaf children's records from leaf16 (Masks64::kLeafInline):
-// one per node id, 16 bytes, so at most 307 MB (a full depth-8 tree).
-int build_leaf16(ort_ctx* ctx) {
-    free_buf(ctx->leaf16);
-    const int64_t n = (int64_t)(ctx->node.bytes / 8);
-    if (!ort::Masks64::kLeafInline || ctx->depth > 8 || n == 0) return ORT_OK;
-    int rc;
-    if ((rc = upload(ctx, ctx->leaf16, nullptr, 16 * (size_t)n))) return rc;
-    hipLaunchKernelGGL(k_leaf16, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                       (const uint2*)ctx->node.p, (const uint4*)ctx->leaf_sph.p, (int64_t)(ctx->leaf_sph.bytes / 16),
-                       (uint4*)ctx->leaf16.p, n);
-    HIPCHK(ctx, hipGetLastError());
-    return ORT_OK;
-}
-
-// Root box for the coherence-sort key: the tree's root node, or the spheres' bounds when
-// there is no tree (brute force).  Only orders work; never affects pixels.
-void set_root_box(ort_ctx* ctx, const float* nmin, const float* nmax, const float* cr, int32_t n) {
-    for (int a = 0; a < 3; ++a) {
-        ctx->root_lo[a] = 0.0f;
-        ctx->root_hi[a] = 0.0f;
-    }
-    if (nmin && nmax) {
-        for (int a = 0; a < 3; ++a) {
-            ctx->root_lo[a] = nmin[a];
-            ctx->root_hi[a] = nmax[a];
-        }
-        return;
-    }
-    for (int32_t i = 0; i < n && cr; ++i)
-        for (int a = 0; a < 3; ++a) {
-            const float lo = cr[4 * (size_t)i + a] - cr[4 * (size_t)i + 3], hi = cr[4 * (size_t)i + a] + cr[4 * (size_t)i + 3];
-            if (i == 0 || lo < ctx->root_lo[a]) ctx->root_lo[a] = lo;
-            if (i == 0 || hi > ctx->root_hi[a]) ctx->root_hi[a] = hi;
-        }
-}
-
-// Spheres -> device (bindings 0, 1 and the .xy of binding 2).
-int upload_spheres(ort_ctx* ctx, const float* cr, const float* ma, const float* fr, int32_t n) {
-    std::vector<float> fr2((size_t)n * 2);
-    for (int32_t i = 0; i < n; ++i) {
-        fr2[2 * (size_t)i] = fr[4 * (size_t)i];
-        fr2[2 * (size_t)i + 1] = fr[4 * (size_t)i + 1];
-    }
-    int rc;
-    if ((rc = upload(ctx, ctx->sph_cr, cr, 16 * (size_t)n))) return rc;
-    if ((rc = upload(ctx, ctx->sph_ma, ma, 16 * (size_t)n))) return rc;
-    if ((rc = upload(ctx, ctx->sph_fr, fr2.data(), 8 * (size_t)n))) return rc;
-    ctx->n_spheres = n;
-    return ORT_OK;
-}
-
-// ort_build_scene: GPU octree build (gpu_build.hip) straight into the kernel layout.
-int build_impl(ort_ctx* ctx, const float* cr, const float* ma, const float* fr, int32_t n, int32_t max_depth,
-               int32_t max_per_node, int32_t keep_tree) {
-    if (n <= 0) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_build_scene: Sphere list is empty");
-    if (!cr || !ma || !fr) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_build_scene: null sphere array");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    free_scene(ctx);
-    int rc;
-    if ((rc = upload_spheres(ctx, cr, ma, fr, n))) return rc;
-    ort::GpuTree t;
-    const std::string e = ort::gpuBuildOctree((const float4*)ctx->sph_cr.p, n, max_depth, max_per_node, ctx->stream, t);
-    if (!e.empty()) {
-        ort::freeGpuTree(t);
-        return fail(ctx, e.find("out of memory") != std::string::npos ? ORT_ERR_OUT_OF_MEMORY : ORT_ERR_INTERNAL,
-                    "ort_build_scene: " + e);
-    }
-    ctx->n_nodes = t.n_nodes;
-    ctx->n_indices = t.n_indices;
-    ctx->depth = t.depth;
-    ctx->ordered = t.ordered;
-    {
-        float lo[3], hi[3];
-        if (hipMemcpy(lo, t.node_min, 12, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(hi, t.node_max, 12, hipMemcpyDeviceToHost) == hipSuccess)
-            set_root_box(ctx, lo, hi, nullptr, 0);
-    }
-    ctx->build_ms = (float)(t.seconds * 1e3);
-    std::string why;
-    ort::CompactDev cd;
-    const bool compact_ok = ctx->force_layout != ORT_LAYOUT_EXPLICIT &&
-                            ort::gpuCompactLayout(t, (const float4*)ctx->sph_cr.p, ORT_COMPACT_MAX_DEPTH, ctx->stream, cd, why);
-    if (compact_ok) {
-        ctx->layout = ORT_LAYOUT_COMPACT;
-        ctx->node = {cd.node, cd.node_bytes};
-        ctx->kid = {cd.kid, cd.node_bytes};
-        ctx->leaf_sph = {cd.leaf_sph, cd.leaf_bytes};
-        ctx->leaf_idx = {cd.leaf_idx, cd.idx_bytes};
-        ctx->planes = {cd.planes, cd.plane_bytes};
-        if ((rc = build_lds_image(ctx)) || (rc = build_nk(ctx)) || (rc = build_leaf16(ctx))) {
-            ort::freeGpuTree(t);
-            return rc;
-        }
-    } else {
-        if (ctx->force_layout == ORT_LAYOUT_COMPACT) {
-            ort::freeGpuTree(t);
-            return fail(ctx, ORT_ERR_UNSUPPORTED, "compact layout forced but not possible: " + why);
-        }
-        ort::ExplicitDev ed;
-        const std::string ee = ort::gpuExplicitLayout(t, ctx->stream, ed);
-        ctx->nodeA = {ed.nodeA, 16 * (size_t)std::max(t.n_nodes, 1)};
-        ctx->nodeB = {ed.nodeB, 16 * (size_t)std::max(t.n_nodes, 1)};
-        ctx->cnt = {ed.cnt, 4 * (size_t)std::max(t.n_nodes, 1)};
-        ctx->indices = {ed.indices, 4 * (size_t)std::max<int64_t>(t.n_indices, 1)};
-        if (!ee.empty()) {
-            ort::freeGpuTree(t);
-            free_scene(ctx);
-            return fail(ctx, ORT_ERR_HIP, "ort_build_scene: " + ee);
-        }
-        ctx->layout = ORT_LAYOUT_EXPLICIT;
-    }
-    if (keep_tree) ctx->tree = t;
-    else ort::freeGpuTree(t);
-    ctx->has_scene = true;
-    return ORT_OK;
-}
-
-int upload_impl(ort_ctx* ctx, const ort::SceneInput& in) {
-    const std::string bad = ort::validateScene(in);
-    if (!bad.empty()) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_upload_scene: " + bad);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    free_scene(ctx);
-    int rc;
-    if ((rc = upload_spheres(ctx, in.sph_cr, in.sph_ma, in.sph_fr, in.n_spheres))) return rc;
-    ctx->n_nodes = in.n_nodes;
-    ctx->n_indices = in.n_indices;
-    ctx->layout = ORT_LAYOUT_EXPLICIT;
-    ctx->depth = 0;
-    set_root_box(ctx, in.n_nodes > 0 ? in.node_min : nullptr, in.n_nodes > 0 ? in.node_max : nullptr, in.sph_cr,
-                 in.n_spheres);
-    if (in.n_nodes > 0) {
-        ort::CompactLayout cl;
-        std::string why;
-        const bool want_compact = ctx->force_layout != ORT_LAYOUT_EXPLICIT;
-        const bool compact_ok = want_compact && ort::buildCompactLayout(in, ORT_COMPACT_MAX_DEPTH, cl, why);
-        if (ctx->force_layout == ORT_LAYOUT_COMPACT && !compact_ok)
-            return fail(ctx, ORT_ERR_UNSUPPORTED, "compact layout forced but not possible: " + why);
-        if (compact_ok) {
-            ctx->layout = ORT_LAYOUT_COMPACT;
-            ctx->depth = cl.depth;
-            ctx->ordered = cl.ordered;
-            if ((rc = upload(ctx, ctx->node, cl.node.data(), 4 * cl.node.size()))) return rc;
-            if ((rc = upload(ctx, ctx->kid, cl.kid.data(), 4 * cl.kid.size()))) return rc;
-            if ((rc = upload(ctx, ctx->leaf_sph, cl.leaf_sph.data(), 4 * cl.leaf_sph.size()))) return rc;
-            if ((rc = upload(ctx, ctx->leaf_idx, cl.leaf_idx.data(), 4 * cl.leaf_idx.size()))) return rc;
-            if ((rc = upload(ctx, ctx->planes, cl.planes.data(), 4 * cl.planes.size()))) return rc;
-            if ((rc = build_lds_image(ctx))) return rc;
-            if ((rc = build_nk(ctx))) return rc;
-            if ((rc = build_leaf16(ctx))) return rc;
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        } else {
-            const int d = ort::treeDepth(in);
-            ctx->depth = d < 0 ? 0 : d;
-            std::vector<float> A(4 * (size_t)in.n_nodes), B(4 * (size_t)in.n_nodes);
-            for (int32_t i = 0; i < in.n_nodes; ++i) {
-                for (int k = 0; k < 3; ++k) {
-                    A[4 * (size_t)i + k] = in.node_min[3 * (size_t)i + k];
-                    B[4 * (size_t)i + k] = in.node_max[3 * (size_t)i + k];
-                }
-                std::memcpy(&A[4 * (size_t)i + 3], &in.co[i], 4);
-                std::memcpy(&B[4 * (size_t)i + 3], &in.oo[i], 4);
-            }
-            if ((rc = upload(ctx, ctx->nodeA, A.data(), 4 * A.size()))) return rc;
-            if ((rc = upload(ctx, ctx->nodeB, B.data(), 4 * B.size()))) return rc;
-            if ((rc = upload(ctx, ctx->cnt, in.cnt, 4 * (size_t)in.n_nodes))) return rc;
-            if ((rc = upload(ctx, ctx->indices, in.indices, 4 * (size_t)in.n_indices))) return rc;
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        }
-    } else {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    ctx->has_scene = true;
-    return ORT_OK;
-}
-
-ort::KScene device_scene(const ort_ctx* c) {
-    ort::KScene S;
-    std::memset(&S, 0, sizeof(S));
-    S.sph_cr = (const float4*)c->sph_cr.p;
-    S.sph_ma = (const float4*)c->sph_ma.p;
-    S.sph_fr = (const float2*)c->sph_fr.p;
-    S.n_spheres = c->n_spheres;
-    S.n_nodes = c->n_nodes;
-    S.node = (const uint2*)c->node.p;
-    S.kid = c->kid_skip ? (const uint2*)c->kid.p : nullptr;
-    S.nk = c->kid_skip == 1 ? (const uint4*)c->nk.p : nullptr;  // 2: the separate arrays (testing)
-    S.nk_bytes = (uint32_t)c->nk.bytes;
-    S.tail_base = (uint32_t)c->n_indices;
-    S.leaf16 = (const uint4*)c->leaf16.p;
-    S.leaf16_bytes = (uint32_t)c->leaf16.bytes;
-    S.leaf_sph = (const float4*)c->leaf_sph.p;
-    S.node_bytes = (uint32_t)c->node.bytes;
-    S.leaf_bytes = (uint32_t)c->leaf_sph.bytes;
-    S.leaf_idx = (const int*)c->leaf_idx.p;
-    S.planes = (const float*)c->planes.p;
-    S.lds_img = (const uint4*)c->lds_img.p;
-    S.lds_img_p16 = (int)(align16(sizeof(float) * (size_t)ort::fast_plane_floats(c->depth)) / 16);
-    S.lds_img_n16 = ort::lds_layout(c->depth, ort::fast_rev_planes(c->depth)).frames / 16;
-    S.lds_rev = (const uint4*)c->lds_rev.p;
-    S.lds_rev_n16 = ort::lds_layout(c->depth, true).frames / 16;
-    S.depth = c->depth;
-    S.nodeA = (const float4*)c->nodeA.p;
-    S.nodeB = (const float4*)c->nodeB.p;
-    S.count = (const int*)c->cnt.p;
-    S.indices = (const int*)c->indices.p;
-    return S;
-}
-
-ort::KCamera to_kcamera(const ort::CameraFrame& f) {
-    ort::KCamera k;
-    k.origin = ort::mk(f.origin[0], f.origin[1], f.origin[2]);
-    k.lowerLeft = ort::mk(f.lowerLeft[0], f.lowerLeft[1], f.lowerLeft[2]);
-    k.horizontal = ort::mk(f.horizontal[0], f.horizontal[1], f.horizontal[2]);
-    k.vertical = ort::mk(f.vertical[0], f.vertical[1], f.vertical[2]);
-    k.u = ort::mk(f.u[0], f.u[1], f.u[2]);
-    k.v = ort::mk(f.v[0], f.v[1], f.v[2]);
-    k.w = ort::mk(f.w[0], f.w[1], f.w[2]);
-    k.lensRadius = f.lensRadius;
-    return k;
-}
-
-// "" or what is wrong with the frame's size and the tile: what the host emulation checks too (it
-// restates the shader, which defines a frame for every sample count).
-std::string check_frame_tile(const ort_params* p, const ort_tile* t) {
-    if (!p || !t) return "null params or tile";
-    if (p->width <= 0 || p->height <= 0) return "width/height must be positive";
-    if (t->width < 0 || t->rows < 0) return "negative tile size";
-    if (t->x0 < 0 || (int64_t)t->x0 + t->width > p->width) return "tile columns outside the frame";
-    if (t->y0 < 0) return "negative y0";
-    if (t->band_height > 0 && t->band_stride < t->band_height) return "band_stride < band_height";
-    return "";
-}
-
-// ... and with the frame's parameters, for the calls that render on the device (include/ort.h
-// ort_params): no samples would leave the output unwritten or finalize stale sums.
-std::string check_params(const ort_params* p, const ort_tile* t) {
-    const std::string bad = check_frame_tile(p, t);
-    if (!bad.empty()) return bad;
-    if (p->num_samples < 1) return "num_samples must be at least 1";
-    return "";
-}
-
-ort::PixelParams pixel_params(const ort_params* p) {
-    ort::PixelParams pp;
-    const ort::CameraFrame f = ort::cameraFrameFromView(p->view, p->camera_position, p->camera_zoom,
-                                                        (float)p->width / (float)p->height);
-    pp.cam = to_kcamera(f);
-    pp.W = p->width;
-    pp.H = p->height;
-    pp.ns = p->num_samples;
-    pp.maxDepth = p->max_depth;
-    return pp;
-}
-
-int ensure(ort_ctx* ctx, DevBuf& b, size_t bytes) {
-    if (b.bytes >= bytes && b.p) return ORT_OK;
-    free_buf(b);
-    HIPCHK(ctx, hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    return ORT_OK;
-}
-
-// The dispatchers below stand in the order of their kernels in the code object (a kernel template
-// is emitted where it is first named): moving one reorders the device code.
-// A runtime int as a template argument: f(std::integral_constant<int, V>) for the first listed V
-// equal to v, the LAST listed one when none is.  Every dispatcher below lists exactly the
-// combinations it compiles: a kernel instance exists only where one of them names it.
-template <int V, int... Rest, class F>
-inline auto pick(int v, F&& f) {
-    if constexpr (sizeof...(Rest) == 0) return f(std::integral_constant<int, V>{});
-    else return v == V ? f(std::integral_constant<int, V>{}) : pick<Rest...>(v, f);
-}
-#define ORT_V(x) decltype(x)::value  // the constant a pick() lambda was handed
-
-// The shade kernel of a bounce: DIRECT, bounce 0 into a tight float tile (ort_render's own output),
-// bounce 0 into any other output, a later bounce.
-hipError_t launch_shade(int mode, bool first, bool direct, const PipeArgs& a, int blocks, hipStream_t s) {
-    const dim3 g(blocks), t(kBlock);
-    const bool tight_f32 = a.out_format == ORT_FORMAT_RGB32F && a.out_place == ORT_PLACE_TILE &&
-                           a.out_pitch == 12u * (unsigned)a.tm.tw;
-    pick<0, 1, 2>(mode, [&](auto MODE) {
-        if (direct) hipLaunchKernelGGL((ort_shade_kernel<ORT_V(MODE), true, true>), g, t, 0, s, a);
-        else if (first && tight_f32) hipLaunchKernelGGL((ort_shade_kernel<ORT_V(MODE), true, false>), g, t, 0, s, a);
-        else if (first) hipLaunchKernelGGL((ort_shade_first_any<ORT_V(MODE)>), g, t, 0, s, a);
-        else hipLaunchKernelGGL((ort_shade_kernel<ORT_V(MODE), false, false>), g, t, 0, s, a);
-    });
-    return hipGetLastError();
-}
-
-// Resident workgroups of a persistent grid (a plain launch: extra groups just start when others
-// finish; no grid-wide synchronisation depends on residency), at most `needed`.
-template <class K>
-int resident_blocks(int device, K kernel, int threads, size_t lds, long long needed) {
-    int per_cu = 0, cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds);
-    const long long b = (long long)std::max(per_cu, 1) * std::max(cus, 1);
-    return (int)std::max(1LL, std::min(b, needed));
-}
-
-// ... of the persistent trace kernel
-int persistent_blocks(int device, bool count, bool deep, int depth, size_t lds, long long needed) {
-    const size_t dlds = lds_bytes(0, depth, false, kRevBounce, kPersistDeepBlock);
-    return pick<1, 0>(count, [&](auto COUNT) {
-        return deep ? resident_blocks(device, ort_trace_persistent<ORT_V(COUNT), true>, kPersistDeepBlock, dlds, needed)
-                    : resident_blocks(device, ort_trace_persistent<ORT_V(COUNT), false>, kBlock, lds, needed);
-    });
-}
-
-// One ort_pixel_paths launch (pm: 0 whole chains, 1 the samples' chunks in parallel, 2 recording or
-// fixup; the variant of the scene's walk: brute force, a deep tree, an LDS-resident scene, or the
-// plain compact walk) over a persistent grid sized by the variant's occupancy, at most `needed`
-// workgroups.
-hipError_t launch_pixel_paths(int pm, int device, int mode, bool deep, bool lds_scene, size_t lds, long long needed,
-                              const PipeArgs& a, hipStream_t s) {
-    const int variant = mode == 2 ? 0 : (deep ? 1 : (lds_scene ? 2 : 3));
-    pick<2, 0, 1>(pm, [&](auto PM) {
-        pick<0, 1, 2, 3>(variant, [&](auto V) {
-            constexpr int MODE = ORT_V(V) == 0 ? 2 : 0;
-            constexpr bool DEEP = ORT_V(V) == 1, LDS = ORT_V(V) == 2;
-            const int g = resident_blocks(device, ort_pixel_paths<MODE, DEEP, LDS, ORT_V(PM)>, kBlock, lds, needed);
-            hipLaunchKernelGGL((ort_pixel_paths<MODE, DEEP, LDS, ORT_V(PM)>), dim3(g), dim3(kBlock), lds, s, a);
-        });
-    });
-    return hipGetLastError();
-}
-
-// The split walks of the listed heavy camera rays (FUSE 1: one bounce, shading fused; 2: bounce
-// 0 of a longer path).
-#ifndef ORT_SPLIT_BLOCKS
-#define ORT_SPLIT_BLOCKS 32  // 1024 heavy rays in flight; more loop
-#endif
-hipError_t launch_trace_split(bool deep, int fmode, const PipeArgs& a, size_t lds, hipStream_t s) {
-    pick<1, 0>(deep, [&](auto DEEP) {
-        pick<1, 2>(fmode, [&](auto FUSE) {
-            hipLaunchKernelGGL((ort_trace_split<ORT_V(DEEP) != 0, ORT_V(FUSE)>), dim3(ORT_SPLIT_BLOCKS), dim3(kBlock), lds, s, a);
-        });
-    });
-    return hipGetLastError();
-}
-
-// The trace launch of a bounce: tile pairs, the persistent kernel over a list, the per-tile
-// kernels of the compact layout, or the explicit-layout / brute-force kernel.
-template <bool COUNT, bool PRIMARY>
-hipError_t launch_trace_p(int mode, const PipeArgs& a, int blocks, int pblocks, size_t lds, hipStream_t s, int fuse) {
-    const dim3 g(blocks), t(kBlock);
-    const int deep = a.S.depth > 8;
-    if (PRIMARY && mode == 0 && a.pair && pblocks == 0)  // tile pairs: blocks = workgroups (one per pair)
-        pick<1, 0>(deep, [&](auto DEEP) {
-            pick<1, 2, 0>(fuse, [&](auto FUSE) {
-                if constexpr (ORT_V(DEEP)) hipLaunchKernelGGL((ort_trace_pair_deep<COUNT, ORT_V(FUSE)>), g, t, lds, s, a);
-                else hipLaunchKernelGGL((ort_trace_pair<COUNT, ORT_V(FUSE)>), g, t, lds, s, a);
-            });
-        });
-    else if (mode == 0 && pblocks > 0 && deep)
-        hipLaunchKernelGGL((ort_trace_persistent<COUNT, true>), dim3(pblocks), dim3(kPersistDeepBlock),
-                           lds_bytes(0, a.S.depth, false, kRevBounce, kPersistDeepBlock), s, a);
-    else if (mode == 0 && pblocks > 0)
-        hipLaunchKernelGGL((ort_trace_persistent<COUNT, false>), dim3(pblocks), t, lds, s, a);
-    else if (mode == 0)
-        pick<1, 0>(deep, [&](auto DEEP) {
-            pick<1, 2, 0>(fuse, [&](auto FUSE) {
-                if constexpr (ORT_V(DEEP)) hipLaunchKernelGGL((ort_trace_compact_deep<COUNT, PRIMARY, ORT_V(FUSE)>), g, t, lds, s, a);
-                else hipLaunchKernelGGL((ort_trace_compact<COUNT, PRIMARY, ORT_V(FUSE)>), g, t, lds, s, a);
-            });
-        });
-    else
-        pick<1, 2>(mode, [&](auto MODE) { hipLaunchKernelGGL((ort_trace_kernel<ORT_V(MODE), COUNT, PRIMARY>), g, t, 0, s, a); });
-    return hipGetLastError();
-}
-
-hipError_t launch_trace(bool count, int mode, bool primary, const PipeArgs& a, int blocks, int pblocks, size_t lds,
-                        hipStream_t s, int fuse) {
-    return pick<1, 0>(count, [&](auto COUNT) {
-        return primary ? launch_trace_p<ORT_V(COUNT) != 0, true>(mode, a, blocks, pblocks, lds, s, fuse)
-                       : launch_trace_p<ORT_V(COUNT) != 0, false>(mode, a, blocks, pblocks, lds, s, 0);
-    });
-}
-
-// The exact walk of the deferred rays: a grid-stride loop over the (usually no) deferred rays; a
-// small grid dispatches fast.  Seven instances: counting renders never fuse bounce 0 of a longer
-// path (fmode 2), and only camera rays fuse at all.
-hipError_t launch_trace_exact(bool count, bool prim, int fmode, const PipeArgs& a, size_t lds, hipStream_t s) {
-    const dim3 g(256), t(kBlock);
-    pick<1, 0>(count, [&](auto COUNT) {
-        constexpr bool C = ORT_V(COUNT) != 0;
-        if (fmode == 1) hipLaunchKernelGGL((ort_trace_exact<C, true, 1>), g, t, lds, s, a);
-        else if (!C && fmode == 2) {
-            if constexpr (!C) hipLaunchKernelGGL((ort_trace_exact<false, true, 2>), g, t, lds, s, a);
-        } else if (prim) hipLaunchKernelGGL((ort_trace_exact<C, true, 0>), g, t, lds, s, a);
-        else hipLaunchKernelGGL((ort_trace_exact<C, false, 0>), g, t, lds, s, a);
-    });
-    return hipGetLastError();
-}
-
-// Whole-pixel paths (ort_pixel_paths): the frame in one launch.  Auto (ORT_OPT_PIXEL_PATHS -1):
-// frames of more than one traversal per pixel on brute force, and on trees of at most
-// kPixelPathsAutoNodes nodes, kPixelPathsAutoNodes5 with 5+ bounces, kPixelPathsAutoNodes8 with
-// 8+ -- where the pipeline's per-bounce launches and sorts cost more than its coherence gains.
-// The crossover follows the bounces: the pipeline pays a launch, a sort and a copy per bounce
-// even when few paths are left, whole-pixel paths only the paths' own work (1080p grid over
-// 1.5-11 M nodes x 1-4 samples x 4-16 bounces, profiles/r06/grid/).
-constexpr long long kPixelPathsAutoNodes = 1ll << 19;   // any bounce depth
-constexpr long long kPixelPathsAutoNodes5 = 1ll << 23;  // maxDepth 5-7
-constexpr long long kPixelPathsAutoNodes8 = 1ll << 24;  // maxDepth 8+ (measured to 11 M nodes)
-#ifndef ORT_PIXEL_LDS_SCENE_BYTES
-#define ORT_PIXEL_LDS_SCENE_BYTES 32768
-#endif
-constexpr int kPixelLdsSceneBytes = ORT_PIXEL_LDS_SCENE_BYTES;  // LDS-resident scene budget (ort_pixel_paths)
-// samples in parallel: device bytes of the per-sample buffers (two end states, the radiance) and
-// the per-slot ones (flags, fixup list); frames above the budget run the pixels' chains whole
-constexpr size_t kSpecBudget = size_t(8) << 30;
-#ifndef ORT_PIXEL_SPEC_CHUNKS
-#define ORT_PIXEL_SPEC_CHUNKS 4
-#endif
-// a pixel's samples in (about) this many chunks of at least kSpecMinChunk samples: a SPEC item
-// is one chunk of a block's pixels -- shorter chains with more chunks, but each item starts with
-// a load of its state and a refill (one-sample chunks: 4 x 4 on 10 spheres at 1080p 0.55 ->
-// 1.69 ms; config.h's 16 x 8 in 2 / 4 / 8 chunks: 1.46 / 1.77 / 1.60x, profiles/r06/ab_spec_*)
-constexpr int kSpecChunks = ORT_PIXEL_SPEC_CHUNKS;
-constexpr int kSpecMinChunk = 4;
-inline int spec_chunk(int ns) { return std::max(kSpecMinChunk, (ns + kSpecChunks - 1) / kSpecChunks); }
-inline int spec_nch(int ns) { return (ns + spec_chunk(ns) - 1) / spec_chunk(ns); }
-#ifndef ORT_PIXEL_SPEC_MOVED_MAX
-#define ORT_PIXEL_SPEC_MOVED_MAX 1000
-#endif
-constexpr long long kSpecMovedMax = ORT_PIXEL_SPEC_MOVED_MAX;
-constexpr float kSpecAutoGain = 1.0f;           // auto keeps speculating when it ran at most this x the whole-chain frame
-constexpr long long kSpecAutoPixels = 1 << 20;  // ... and without timing events, on frames of at most this many pixels
-inline size_t spec_bytes(size_t slots, int ns) { return slots * ((size_t)spec_nch(ns) * 16 + (size_t)ns * 12 + 28); }
-bool use_pixel_paths(const ort_ctx* ctx, int mode, int ns, int maxd);
-
-
-// FNV-1a of the frame shape and scene: the previous-frame hints (list lengths, walk costs)
-// belong to one of these
-unsigned long long frame_sig(const ort_ctx* ctx, const ort_params* p, const ort_tile* t) {
-    const long long v[] = {p->width, p->height, p->num_samples, p->max_depth, t->x0, t->width, t->y0,
-                           t->rows, t->band_height, t->band_stride, ctx->n_nodes, ctx->n_spheres,
-                           (long long)ctx->n_indices, ctx->xcd_swizzle, ctx->tile_pairs};
-    unsigned long long sig = 1469598103934665603ull;
-    for (long long x : v) sig = (sig ^ (unsigned long long)x) * 1099511628211ull;
-    return sig;
-}
-
-bool use_pixel_paths(const ort_ctx* ctx, int mode, int ns, int maxd) {
-    if (mode == 1 || maxd < 1 || (ns == 1 && maxd == 1) || ctx->pixel_paths == 0) return false;
-    if (ctx->pixel_paths > 0) return true;
-    // 1080p, whole-pixel paths over the pipeline: 8 bounces 1.02-1.50x from 1.5 to 11 M nodes
-    // (1 to 4 samples), 5 bounces 1.09-1.10x to 5 M, 1.00x at 8.3 M, 0.95x at 11 M; 4 bounces
-    // 0.74-1.02x from 1.5 M nodes on, 1.09x at 209 k (profiles/r06/grid/)
-    const long long limit = maxd >= 8 ? kPixelPathsAutoNodes8 : (maxd >= 5 ? kPixelPathsAutoNodes5 : kPixelPathsAutoNodes);
-    return mode == 2 || ctx->n_nodes <= limit;
-}
-
-// Where the kernels write a frame (ort_output, checked and resolved by render_impl): data on the
-// device, the row pitch in bytes.
-struct DevOutput {
-    void* data;
-    long long pitch;
-    int format, place;
-};
-inline int format_bpp(int format) { return format == ORT_FORMAT_RGBA8 ? 4 : 12; }
-inline void set_output(PipeArgs& a, const DevOutput& o) {
-    a.out = o.data;
-    a.out_pitch = (unsigned)o.pitch;
-    a.out_format = o.format;
-    a.out_place = o.place;
-}
-
-// The argument block's part that both render paths fill alike: camera, scene, tile, grid, output.
-PipeArgs base_args(const ort_ctx* ctx, const ort_params* p, const ort_tile* t, const DevOutput& o, int tilesX,
-                   int tilesY, long long blocks) {
-    PipeArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.pp = pixel_params(p);
-    a.S = device_scene(ctx);
-    a.tm = {t->x0, t->width, t->y0, t->rows, t->band_height, t->band_stride};
-    a.tilesX = tilesX;
-    a.tilesY = tilesY;
-    a.total = (int)(blocks * kBlock);
-    a.exact_only = ctx->exact_only || !ctx->ordered;
-    set_output(a, o);
-#if ORT_ANALYSIS
-    a.wclock = (ulonglong4*)ctx->wclock;  // ORT_PERSIST_CLOCK / ORT_PIXEL_CLOCK builds (tools/*_clock.py)
-    a.wclock_n = (int)ctx->wclock_n;
-#endif
-    return a;
-}
-
-// Two sets of 16 counters (deferred count, persistent cursor, heavy list) in defer_count: a launch
-// uses one and its exact kernel (or ort_pixel_paths' last workgroup) zeroes the other for the next
-// launch; a memset re-zeroes both after a failed render or a new buffer (sync_ok).  fresh: it did.
-int begin_counter_sets(ort_ctx* ctx, hipStream_t s, bool& fresh) {
-    fresh = !ctx->sync_ok;
-    if (fresh) {
-        HIPCHK(ctx, hipMemsetAsync(ctx->defer_count.p, 0, 128, s));
-        ctx->sync_set = 0;
-        ctx->pre_ok = false;  // a failed render may not have listed the next frame's heavy rays
-    }
-    ctx->sync_ok = false;  // until this render has enqueued all its launches
-    return ORT_OK;
-}
-
-// The dynamic LDS of an ort_pixel_paths launch on ctx's scene, and whether the scene itself lives
-// there (lds_scene; then a's lds_* fields say where).
-size_t pixel_paths_lds(const ort_ctx* ctx, int mode, PipeArgs& a, bool& lds_scene) {
-    size_t lds = mode == 0 ? lds_bytes(0, ctx->depth, true) : 0;
-    // an LDS-resident scene: node records + kid entries (16 B per node) and the leaf spheres
-    // (16 B per entry: objectIndices, then the per-sphere tail), when they fit the budget
-    const size_t nk_b = 16 * (size_t)ctx->n_nodes, sph_b = 16 * ((size_t)ctx->n_indices + (size_t)ctx->n_spheres);
-    lds_scene = mode == 0 && ctx->depth <= 8 && a.S.nk && ctx->pixel_lds_scene && nk_b + sph_b <= (size_t)kPixelLdsSceneBytes;
-    if (lds_scene) {
-        a.lds_nk_off = (int)align16(lds);
-        a.lds_sph_off = (int)(a.lds_nk_off + nk_b);
-        a.lds_nk_n16 = (int)(nk_b / 16);
-        a.lds_sph_n16 = (int)(sph_b / 16);
-        lds = (size_t)a.lds_sph_off + sph_b;
-    }
-    return lds;
-}
-
-// The frame as one ort_pixel_paths launch (use_pixel_paths); dout: the frame on the device.
-int render_pixel_paths(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int mode, const DevOutput& dout,
-                       hipStream_t s) {
-    const int tilesX = (t->width + 15) / 16, tilesY = (t->rows + 15) / 16;
-    const long long blocks = (long long)tilesX * tilesY;
-    PipeArgs a = base_args(ctx, p, t, dout, tilesX, tilesY, blocks);
-    // the cursor and done count: this frame's counter set (zero; the kernel's last workgroup
-    // zeroes them again, so the set stays the pipeline's next one)
-    int rc;
-    bool fresh;
-    if ((rc = begin_counter_sets(ctx, s, fresh))) return rc;
-    if (fresh) ctx->pp_sig = 0;  // (the class lists' counts re-zeroed below)
-    a.sync = (int*)ctx->defer_count.p + 16 * ctx->sync_set;
-    const unsigned long long sig = frame_sig(ctx, p, t);
-    // samples in parallel (ORT_OPT_PIXEL_SPECULATE, ort_pixel_paths<..., SPEC>): from the second
-    // frame of a shape on, when the per-sample state buffers fit kSpecBudget; the first frame
-    // runs the pixels' chains whole and records their samples' end states
-    const int ns = p->num_samples;
-    const size_t slots = (size_t)a.total;
-    const int nch = spec_nch(ns);
-    const bool timed = !((ctx->debug_flags & 1) || !ctx->launch_times);  // per-launch events
-    const bool spec_on = ctx->pixel_spec != 0 && nch > 1 && spec_bytes(slots, ns) <= kSpecBudget;
-    if (!spec_on) ctx->sp_sig = 0;
-    bool spec_frame = false;
-    float2 *sp_prev = nullptr, *sp_cur = nullptr;
-    if (spec_on) {
-        const void* had = ctx->spst.p;
-        if ((rc = ensure(ctx, ctx->spst, 2 * sizeof(float2) * (size_t)nch * slots)) ||
-            (rc = ensure(ctx, ctx->spcol, 3 * sizeof(float) * (size_t)ns * slots)) ||
-            (rc = ensure(ctx, ctx->spfix, (2 * sizeof(int) + sizeof(float2) + 3 * sizeof(float)) * slots)) ||
-            (rc = ensure(ctx, ctx->spfixn, 64)))
-            return rc;
-        if (ctx->spst.p != had) ctx->sp_sig = 0;  // reallocated: no recorded states
-        const long long pixels = (long long)t->width * t->rows;
-        if (ctx->sp_sig != sig) {  // a fresh start: an empty fixup list, nothing moved
-            HIPCHK(ctx, hipMemsetAsync(ctx->spfixn.p, 0, 64, s));
-            ctx->sp_tune = 0;
-            // untimed contexts cannot compare: speculate on frames of at most kSpecAutoPixels
-            ctx->sp_use = ctx->pixel_spec > 0 || timed || pixels <= kSpecAutoPixels;
-        }
-        if (ctx->sp_tune >= 3 && ctx->sp_tune < 5 && ctx->frames - ctx->sp_tframe >= ort_ctx::kRing - 2)
-            ctx->sp_tune = 2;  // the measured frames' timing slots are being reused: measure again
-        if (ctx->pixel_spec < 0 && ctx->sp_tune == 4) {  // auto: a measured whole-chain frame against a measured SPEC frame
-            float tw = 0.0f, tsp = 0.0f, x = 0.0f;
-            bool ok = hipEventQuery(ctx->tr1[ctx->sp_tslot[1]][2]) == hipSuccess;
-            for (int j = 0; ok && j < 3; ++j) {
-                ok = hipEventElapsedTime(&x, ctx->tr0[ctx->sp_tslot[1]][j], ctx->tr1[ctx->sp_tslot[1]][j]) == hipSuccess;
-                tsp += x;
-            }
-            if (ok) ok = hipEventElapsedTime(&tw, ctx->tr0[ctx->sp_tslot[0]][0], ctx->tr1[ctx->sp_tslot[0]][0]) == hipSuccess;
-            if (ok) {
-                ctx->sp_use = tsp < kSpecAutoGain * tw;
-                ctx->sp_tune = 5;
-            }
-        }
-        spec_frame = ctx->sp_sig == sig && ctx->sp_use &&
-                     !(ctx->pixel_spec < 0 && timed && ctx->sp_tune == 2);  // auto: the measured whole-chain frame
-        a.sp_ctl = (int*)ctx->spfixn.p;
-        float2* st0 = (float2*)ctx->spst.p;
-        sp_prev = ctx->sp_par ? st0 + (size_t)nch * slots : st0;
-        sp_cur = ctx->sp_par ? st0 : st0 + (size_t)nch * slots;
-        a.sp_chunk = spec_chunk(ns);
-        a.sp_nch = nch;
-    }
-    // heavy blocks first (ORT_OPT_PIXEL_HEAVY_FIRST; auto: several samples -- a pixel's chain is
-    // then long enough for the frame's tail to matter, while one-sample frames keep tile order's
-    // locality: 1080p 1 x 4 on 10k spheres 0.89x in heavy-first order, profiles/r06/ab_blk_*);
-    // not in a frame of parallel samples (nothing there is as long as a pixel's chain)
-    const bool heavy_first = !spec_frame &&
-                             (ctx->pixel_heavy_first > 0 || (ctx->pixel_heavy_first < 0 && p->num_samples > 1));
-    if (ORT_PIXEL_LPT && !heavy_first && !spec_frame) ctx->pp_sig = 0;
-    if (ORT_PIXEL_LPT && heavy_first) {  // last frame's class lists (same shape) and this frame's
-        const size_t nb = (size_t)blocks * (kBlock / 64), cnt_b = 2 * kPixelClasses * sizeof(int);
-        if ((rc = ensure(ctx, ctx->pplist, 2 * kPixelClasses * 4 * nb)) || (rc = ensure(ctx, ctx->ppcnt, cnt_b)) ||
-            (rc = ensure(ctx, ctx->ppcost, 8 * nb)))
-            return rc;
-        if (ctx->pp_sig == 0 || ctx->pp_sig != sig) {  // no lists of this shape: zero counts and accumulators
-            HIPCHK(ctx, hipMemsetAsync(ctx->ppcnt.p, 0, cnt_b, s));
-            HIPCHK(ctx, hipMemsetAsync(ctx->ppcost.p, 0, 8 * nb, s));
-        }
-        const int w = ctx->pp_par, r = w ^ 1;
-        int* lists = (int*)ctx->pplist.p;
-        int* cnt = (int*)ctx->ppcnt.p;
-        a.pl_stride = (int)nb;
-        a.pl_w = lists + (size_t)w * kPixelClasses * nb;
-        a.pl_wcnt = cnt + kPixelClasses * w;
-        a.pl_rcnt = cnt + kPixelClasses * r;
-        a.pl_cost = (unsigned long long*)ctx->ppcost.p;
-        a.pl_r = (ctx->pp_sig == sig) ? lists + (size_t)r * kPixelClasses * nb : nullptr;
-        ctx->pp_par = r;
-        ctx->pp_sig = sig;
-    }
-    const bool deep = ctx->depth > 8;
-    bool lds_scene;
-    const size_t lds = pixel_paths_lds(ctx, mode, a, lds_scene);
-    const int fslot = (int)(ctx->frames % ort_ctx::kRing);
-    ctx->tseg[fslot] = 0;
-    const int nseg = spec_frame ? 3 : 1;  // SPEC: the samples, the resolve, the fixup list
-    for (int j = 0; timed && j < nseg; ++j)
-        if (!ctx->tr0[fslot][j]) {
-            HIPCHK(ctx, hipEventCreate(&ctx->tr0[fslot][j]));
-            HIPCHK(ctx, hipEventCreate(&ctx->tr1[fslot][j]));
-        }
-    ctx->ev0_last = timed ? ctx->tr0[fslot][0] : ctx->ev0;  // the frame's start is its trace launch's
-    HIPCHK(ctx, hipEventRecord(ctx->ev0_last, s));
-    if (!spec_frame) {  // every pixel's whole chain (recording its samples' end states when spec_on)
-        a.sp_cur = sp_cur;
-        const bool rec = spec_on && ctx->sp_use;  // (auto found speculation slower on this shape: no recording)
-        const hipError_t e = launch_pixel_paths(rec ? 2 : 0, ctx->device, mode, deep, lds_scene, lds, blocks, a, s);
-        if (e != hipSuccess) return hip_fail(ctx, e, "ort_pixel_paths launch");
-        if (timed) HIPCHK(ctx, hipEventRecord(ctx->tr1[fslot][0], s));
-        if (rec && timed && ctx->sp_tune == 0) ctx->sp_tune = 1;  // auto: a shape's first frame (not measured)
-        if (rec && timed && ctx->sp_tune == 2) {  // auto: this frame's time is the whole-chain side
-            ctx->sp_tslot[0] = fslot;
-            ctx->sp_tframe = ctx->frames;
-            ctx->sp_tune = 3;
-        }
-        if (rec && ctx->sp_sig == sig) {  // how many pixels moved since last frame (mode word 0: count)
-            int* cnt = (int*)ctx->spfixn.p + 1;
-            a.sp_prev = sp_prev;
-            HIPCHK(ctx, hipMemsetAsync(cnt, 0, 2 * sizeof(int), s));
-            hipLaunchKernelGGL(ort_sample_moved, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, a, cnt);
-            hipError_t e2;
-            if ((e2 = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e2, "ort_sample_moved launch");
-        }
-    } else {
-        int* fx = (int*)ctx->spfix.p;
-        a.sp_prev = sp_prev;
-        a.sp_cur = sp_cur;
-        a.sp_col = (float*)ctx->spcol.p;
-        a.fx_n = (int*)ctx->spfixn.p;
-        a.fx_slot = fx;
-        a.fx_s0 = fx + slots;
-        a.fx_st = (float2*)(fx + 2 * slots);
-        a.fx_col = (float*)(fx + 4 * slots);
-        PipeArgs as = a;  // the samples: no fixup list; heavy blocks first by the lists the last
-        as.fx_slot = nullptr;  // whole-chain frame of this shape wrote (read only: SPEC frames keep them)
-        if (ORT_PIXEL_LPT && ctx->pp_sig == sig && ctx->pplist.p) {
-            const size_t nbk = (size_t)blocks * (kBlock / 64);
-            const int r = ctx->pp_par ^ 1;
-            as.pl_stride = (int)nbk;
-            as.pl_r = (int*)ctx->pplist.p + (size_t)r * kPixelClasses * nbk;
-            as.pl_rcnt = (int*)ctx->ppcnt.p + kPixelClasses * r;
-        }
-        hipLaunchKernelGGL(ort_sample_decide, dim3(1), dim3(64), 0, s, a.sp_ctl, (long long)t->width * t->rows, kSpecMovedMax);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(ctx, e, "ort_sample_decide launch");
-        e = launch_pixel_paths(1, ctx->device, mode, deep, lds_scene, lds, blocks * nch, as, s);
-        if (e != hipSuccess) return hip_fail(ctx, e, "ort_pixel_paths (samples) launch");
-        if (timed) HIPCHK(ctx, hipEventRecord(ctx->tr1[fslot][0], s));
-        if (timed) HIPCHK(ctx, hipEventRecord(ctx->tr0[fslot][1], s));
-        hipLaunchKernelGGL(ort_sample_resolve, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, a);
-        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, "ort_sample_resolve launch");
-        if (timed) HIPCHK(ctx, hipEventRecord(ctx->tr1[fslot][1], s));
-        if (timed) HIPCHK(ctx, hipEventRecord(ctx->tr0[fslot][2], s));
-        // the fixup list (the workgroups beyond what it needs leave at once); in a fall-back frame
-        // every pixel's chain, then the count of the pixels that moved
-        e = launch_pixel_paths(2, ctx->device, mode, deep, lds_scene, lds, blocks, a, s);
-        if (e != hipSuccess) return hip_fail(ctx, e, "ort_pixel_paths (fixup) launch");
-        if (timed) HIPCHK(ctx, hipEventRecord(ctx->tr1[fslot][2], s));
-        hipLaunchKernelGGL(ort_sample_moved, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, a, a.sp_ctl + 1);
-        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, "ort_sample_moved launch");
-        if (timed && ctx->sp_tune == 1) ctx->sp_tune = 2;  // auto: the first speculating frame (not measured)
-        if (timed && ctx->sp_tune == 3) {  // auto: ... and this one's the speculating side
-            ctx->sp_tslot[1] = fslot;
-            ctx->sp_tune = 4;
-        }
-    }
-    if (spec_on) {  // this frame's end states are the next frame's
-        ctx->sp_par ^= 1;
-        ctx->sp_sig = sig;
-    }
-    if (timed) {
-        ctx->tseg[fslot] = nseg;
-        ctx->frames += 1;
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, s));
-    ctx->timed = true;
-    ctx->sync_ok = true;
-    return ORT_OK;
-}
-
-// The frame's copy to a host output (the tight scratch frame; row by row where the caller gave a
-// pitch), or the wait of a synchronous device-output call.
-int finish_output(ort_ctx* ctx, const ort_output* o, const DevOutput& dout, const ort_tile* t, long long host_pitch,
-                  void* stream, hipStream_t s) {
-    if (!o->is_device) {
-        const size_t row_bytes = (size_t)t->width * (size_t)format_bpp(o->format);
-        if ((size_t)host_pitch == row_bytes)
-            HIPCHK(ctx, hipMemcpyAsync(o->data, dout.data, row_bytes * (size_t)t->rows, hipMemcpyDeviceToHost, s));
-        else
-            HIPCHK(ctx, hipMemcpy2DAsync(o->data, (size_t)host_pitch, dout.data, row_bytes, row_bytes, (size_t)t->rows,
-                                         hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-    } else if (!stream) {
-        HIPCHK(ctx, hipStreamSynchronize(s));
-    }
-    return ORT_OK;
-}
-
-// "" or what is wrong with the output description (every case before anything is launched).
-std::string check_output(const ort_params* p, const ort_tile* t, const ort_output* o) {
-    if (!o) return "null output";
-    if (o->format != ORT_FORMAT_RGB32F && o->format != ORT_FORMAT_RGBA8) return "output format: unknown ORT_FORMAT_*";
-    if (o->placement != ORT_PLACE_TILE && o->placement != ORT_PLACE_FRAME)
-        return "output placement: unknown ORT_PLACE_*";
-    if (o->reserved != 0) return "output reserved must be 0";
-    if (o->placement == ORT_PLACE_FRAME && !o->is_device)
-        return "output placement: ORT_PLACE_FRAME needs device output (is_device)";
-    const long long row_bytes =
-        (long long)(o->placement == ORT_PLACE_FRAME ? p->width : t->width) * format_bpp(o->format);
-    if (o->row_pitch_bytes % 4 != 0) return "output row_pitch_bytes must be a multiple of 4";
-    if (o->row_pitch_bytes > 0x7fffffffLL || row_bytes > 0x7fffffffLL)
-        return "output row_pitch_bytes: a row of at most 2^31 - 1 bytes";
-    if (o->row_pitch_bytes != 0 && o->row_pitch_bytes < row_bytes)
-        return "output row_pitch_bytes is below the row's " + std::to_string(row_bytes) + " bytes";
-    if (((uintptr_t)o->data & 3) != 0) return "output data must be 4-byte aligned";
-    return "";
-}
-
-int render_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, const ort_output* o, void* stream,
-                unsigned long long* dcounters) {
-    const std::string bad = check_params(p, t);
-    if (!bad.empty()) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_render: " + bad);
-    const std::string bad_out = check_output(p, t, o);
-    if (!bad_out.empty()) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_render: " + bad_out);
-    void* const out = o->data;
-    const int out_is_device = o->is_device;
-    if (!ctx->has_scene) return fail(ctx, ORT_ERR_NO_SCENE, "ort_render: no scene uploaded");
-    const int mode = (p->use_octree == 1) ? (ctx->layout == ORT_LAYOUT_COMPACT ? 0 : 1) : 2;
-    if (mode != 2 && ctx->n_nodes <= 0) return fail(ctx, ORT_ERR_NO_SCENE, "ort_render: scene has no octree");
-    const size_t pix = (size_t)t->width * (size_t)t->rows;
-    if (!out && pix > 0) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_render: null output");
-    if (pix == 0) return ORT_OK;
-    const int tilesX = (t->width + 15) / 16, tilesY = (t->rows + 15) / 16;
-    // tile pairs (ORT_OPT_TILE_PAIRS; the compact layout, trees of 4+ levels: cost_order_pair's
-    // scratch): the slot blocks of a pair are consecutive, a last odd column's second tile a hole
-    // (auto: on large tiles, and on any tile whose caller turned the split walks off -- frames in
-    // flight fill the tail, and pairs then pay on small tiles too: 1/4 band at 3 in flight +4 %)
-    const bool pairs = mode == 0 && ctx->depth >= 4 &&
-                       (ctx->tile_pairs > 0 ||
-                        (ctx->tile_pairs < 0 && ((long long)pix >= kPairsAutoPixels || ctx->split_steps == 0)));
-    const int gridX = pairs ? (tilesX + 1) / 2 : tilesX;
-    const long long blocks = (long long)(pairs ? 2 * gridX : tilesX) * tilesY;
-    if (blocks * kBlock > 0x7fffffffLL) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_render: tile too large");
-    const size_t slots = (size_t)blocks * kBlock;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    // the rows' pitch: the caller's, or tight (tile rows, or the frame's under frame placement)
-    const long long tight =
-        (long long)(o->placement == ORT_PLACE_FRAME ? p->width : t->width) * format_bpp(o->format);
-    const long long pitch = o->row_pitch_bytes ? (long long)o->row_pitch_bytes : tight;
-    DevOutput dout = {out, pitch, o->format, o->placement};
-    int rc;
-    if (!out_is_device) {  // a tight scratch frame on the device, copied out (finish_output)
-        if ((rc = ensure(ctx, ctx->scratch_out, (size_t)format_bpp(o->format) * pix))) return rc;
-        dout.data = ctx->scratch_out.p;
-        dout.pitch = tight;
-    }
-    const int ns = p->num_samples, maxd = p->max_depth;
-    const bool direct = (ns == 1 && maxd == 1);
-    if (!dcounters && use_pixel_paths(ctx, mode, ns, maxd)) {  // the frame in one launch
-        if ((rc = ensure(ctx, ctx->defer_count, 128)) || (rc = render_pixel_paths(ctx, p, t, mode, dout, s))) return rc;
-        return finish_output(ctx, o, dout, t, pitch, stream, s);
-    }
-    if ((rc = ensure(ctx, ctx->hit, 8 * slots)) || (rc = ensure(ctx, ctx->defer_list, 4 * slots)) ||
-        (rc = ensure(ctx, ctx->defer_count, 128)))
-        return rc;
-    if (!direct || ctx->persistent) {
-        if ((rc = ensure(ctx, ctx->po, 16 * slots)) || (rc = ensure(ctx, ctx->pd, 16 * slots)) ||
-            (rc = ensure(ctx, ctx->prng, 8 * slots)) || (rc = ensure(ctx, ctx->pc, 16 * slots)) ||
-            (rc = ensure(ctx, ctx->pcol, 16 * slots)))
-            return rc;
-    }
-    const bool pers_bounce = ctx->persistent == 2;  // persistent only for the bounce >= 1 lists
-    const bool compact = !direct && p->max_depth > 1;
-    // primary-ray mode (1 sample, 1 bounce) on the compact layout: the trace kernels shade
-    const bool fuse = direct && mode == 0;
-    const bool sorted = compact && ctx->sort_paths == 1;   // radix sort of every slot's key
-    const bool listsort = compact && ctx->sort_paths == 2; // sort of the appended list (its length read back)
-    // bounce 0 of a multi-bounce frame: the trace kernels shade their camera rays into the path
-    // state and append the paths that go on (no hit records, no shade launch: C5 -0.7 ms)
-    const bool fuse_first = compact && !sorted && mode == 0 && !dcounters;
-    size_t qtemp_bytes = 0;
-    if (compact) {
-        qtemp_bytes = (sorted || listsort) ? ort::sortAliveTempBytes((int)slots) : 0;
-        if ((rc = ensure(ctx, ctx->qlist, 4 * slots)) || (rc = ensure(ctx, ctx->qlist2, 4 * slots)) ||
-            (rc = ensure(ctx, ctx->qcount, 64)) ||
-            (rc = ensure(ctx, ctx->qtemp, std::max<size_t>(qtemp_bytes, 16))))
-            return rc;
-        if (sorted && ((rc = ensure(ctx, ctx->skeys, 4 * slots)) || (rc = ensure(ctx, ctx->skeys2, 4 * slots)) ||
-                       (rc = ensure(ctx, ctx->svals, 4 * slots))))
-            return rc;
-        if (listsort && ((rc = ensure(ctx, ctx->skeys, 4 * slots)) || (rc = ensure(ctx, ctx->skeys2, 4 * slots)) ||
-                         (rc = ensure(ctx, ctx->svals, 4 * slots))))
-            return rc;
-        if (listsort) {  // the list-length hints belong to one frame shape and scene
-            const unsigned long long sig = frame_sig(ctx, p, t);
-            if (sig != ctx->hint_sig) {
-                int bank = -1;
-                for (int i = 1; i <= ort_ctx::kHintBanks && bank < 0; ++i) {
-                    const int c = (ctx->hint_bank + i) % ort_ctx::kHintBanks;
-                    if (!ctx->hint_ev_used[c] || hipEventQuery(ctx->hint_ev[c]) == hipSuccess) bank = c;
-                }
-                if (bank < 0) {  // every bank still awaits copies (several shape changes in flight)
-                    bank = (ctx->hint_bank + 1) % ort_ctx::kHintBanks;
-                    HIPCHK(ctx, hipEventSynchronize(ctx->hint_ev[bank]));
-                }
-                ctx->hint_bank = bank;
-                for (int i = 0; i < ort_ctx::kHints; ++i) ctx->alive_host[bank * ort_ctx::kHints + i] = -1;
-                ctx->hint_sig = sig;
-            }
-        }
-        if (sorted || listsort) {  // the key tables of the current root box (built once per scene)
-            const float box[6] = {ctx->root_lo[0], ctx->root_lo[1], ctx->root_lo[2],
-                                  ctx->root_hi[0], ctx->root_hi[1], ctx->root_hi[2]};
-            if (!ctx->key_spread.p || std::memcmp(box, ctx->spread_box, sizeof box) != 0) {
-                if ((rc = ensure(ctx, ctx->key_spread, 4 * (size_t)ort::kSpreadWords))) return rc;
-                std::vector<uint32_t> tab((size_t)ort::kSpreadWords);
-                ort::mortonSpread(ort::mortonPlan(ctx->root_lo, ctx->root_hi), tab.data());
-                HIPCHK(ctx, hipMemcpy(ctx->key_spread.p, tab.data(), 4 * tab.size(), hipMemcpyHostToDevice));
-                std::memcpy(ctx->spread_box, box, sizeof box);
-            }
-        }
-    }
-    PipeArgs a = base_args(ctx, p, t, dout, gridX, tilesY, blocks);
-    a.pair = pairs ? 1 : 0;
-    a.swizzle = ctx->xcd_swizzle >= 0 ? ctx->xcd_swizzle : ((!pairs && (long long)pix <= kRasterAutoPixels) ? 0 : 2);
-    a.xrun_log2 = xcd_run_log2(gridX);
-    a.refill = ctx->refill;
-    a.hit = (int2*)ctx->hit.p;
-    a.defer_list = (int*)ctx->defer_list.p;
-    bool fresh;
-    if ((rc = begin_counter_sets(ctx, s, fresh))) return rc;
-    a.sync = (int*)ctx->defer_count.p;
-    a.po = (float4*)ctx->po.p;
-    a.pd = (float4*)ctx->pd.p;
-    a.pc = (float4*)ctx->pc.p;
-    a.prng = (float2*)ctx->prng.p;
-    a.pcol = (float4*)ctx->pcol.p;
-    a.counters = dcounters;
-    a.mp = ort::mortonPlan(ctx->root_lo, ctx->root_hi);
-    // with bounce 0 shaded in the trace kernels every pixel's path ends in a kernel that knows
-    // its pixel, so the last sample writes the final pixels itself (no finalize pass)
-    a.final_out = fuse_first ? 1 : 0;
-    a.key_spread = (const uint32_t*)ctx->key_spread.p;
-    // the cost order: the per-workgroup camera-ray kernels (ort_trace_compact[_deep]) only
-    // the camera moved since this context's last rendered frame (counting renders leave the
-    // record alone): heavy priority here and heavy-first's bounce classes below both gate on it,
-    // whether or not the cost order is on
-    const bool cam_moved = mode == 0 && std::memcmp(&ctx->prio_cam, &a.pp.cam, sizeof(ort::KCamera)) != 0;
-    if (mode == 0 && !dcounters) ctx->prio_cam = a.pp.cam;
-    if (mode == 0 && ctx->cost_order && ctx->depth >= 2) {
-        if ((rc = ensure(ctx, ctx->pcost, 2 * slots))) return rc;
-        const unsigned long long sig = frame_sig(ctx, p, t);
-        if (sig != ctx->cost_sig) {  // a new shape: tile order for the first frame
-            HIPCHK(ctx, hipMemsetAsync(ctx->pcost.p, 0, 2 * slots, s));
-            ctx->cost_sig = sig;
-        }
-        a.pcost = (uint16_t*)ctx->pcost.p;
-        // heavy priority only for a camera that has not moved since this context's last frame:
-        // after a move the per-slot steps are one frame stale (a pixel's walk cost follows its
-        // pixel-seeded lens/jitter sample more than the scene: same-slot hints keep an in-block
-        // correlation of 0.82 with the new walks, reprojected ones 0.05 -- profiles/r05_moving_*),
-        // and raising the wrong waves costs: C3 moving frames 1.855 -> 1.798 ms without it
-        // (profiles/r05_moving_shift_c3.log), static frames unchanged
-        a.prio_steps = cam_moved ? 0 : ctx->heavy_prio;
-    }
-    // split walks of the heavy camera rays (1 sample; the production kernels, bounce 0)
-    const int split_steps = ctx->split_steps >= 0 ? ctx->split_steps
-                                                  : ((long long)pix <= kSplitAutoPixels ? kSplitAutoSteps : 0);
-    const bool split = (fuse || fuse_first) && a.pcost && split_steps > 0 && !dcounters && ns == 1;
-    if (!split) ctx->pre_ok = false;  // (a queued heavy list is only for the next split frame)
-    if (split) {
-        if (!ctx->aux_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
-        if ((rc = ensure(ctx, ctx->hbits, 4 * (slots / 32 + 1))) || (rc = ensure(ctx, ctx->hlist, 4 * (size_t)ort_ctx::kSplitCap)) ||
-            (rc = ensure(ctx, ctx->hcnt, 64)))
-            return rc;
-        a.hlist = (const int*)ctx->hlist.p;
-        a.hcap = ort_ctx::kSplitCap;
-        // the subtrees dealt to the lanes: ~5 levels above the leaves (a depth-8 tree: level 3)
-        a.split_level = ctx->split_level > 0 ? ctx->split_level : std::max(1, ctx->depth - 5);
-    }
-    // heavy first: the bounce >= 1 lists of the persistent trace (sorted, default path)
-    const int nbc = std::min(ns * (maxd > 0 ? maxd : 1), ort_ctx::kCostBounces);  // recorded bounce indices
-    uint16_t* bcost = nullptr;
-    if (listsort && mode == 0 && pers_bounce && ctx->heavy_first > 0) {
-        if ((rc = ensure(ctx, ctx->bcost, 2 * slots * (size_t)nbc))) return rc;
-        const unsigned long long sig = frame_sig(ctx, p, t);
-        if (sig != ctx->bcost_sig) {  // a new shape: no heavy walks known
-            HIPCHK(ctx, hipMemsetAsync(ctx->bcost.p, 0, 2 * slots * (size_t)nbc, s));
-            ctx->bcost_sig = sig;
-        }
-        bcost = (uint16_t*)ctx->bcost.p;
-        a.heavy = ctx->heavy_first;
-    }
-    // ... whose classes are read only while the camera stands still (the steps are recorded
-    // always): after a move last frame's bounce walks are not this frame's, and sorting stale
-    // heavy paths first cost C5's moving frames 0.8 % (1568 -> 1556 Mrays/s, bench --opt HEAVY_FIRST=0)
-#ifndef ORT_HEAVY_FIRST_STATIC_ONLY
-#define ORT_HEAVY_FIRST_STATIC_ONLY 1
-#endif
-#ifndef ORT_GEO_ALWAYS
-#define ORT_GEO_ALWAYS 0  // analysis: the rays' own classes on every frame (tools/ab_stream.py)
-#endif
-    const uint16_t* bcost_rd = ((ORT_HEAVY_FIRST_STATIC_ONLY && cam_moved) || ORT_GEO_ALWAYS) ? nullptr : bcost;
-#ifndef ORT_GEO_HEAVY
-#define ORT_GEO_HEAVY 1
-#endif
-    if (ORT_GEO_HEAVY && bcost && !bcost_rd) {  // moved: classes from the rays themselves (geo_class_bits)
-        a.geo_heavy = 1;
-        float m = 3.0e38f;
-        for (int q = 0; q < 3; ++q) {
-            a.gbox[q] = ctx->root_lo[q];
-            a.gbox[3 + q] = ctx->root_hi[q];
-            m = std::min(m, ctx->root_hi[q] - ctx->root_lo[q]);
-        }
-#ifndef ORT_GEO_T
-#define ORT_GEO_T 1.2f, 2.7f, 6.8f  // the class thresholds, in units of the box's smallest extent
-#endif
-        const float gt[3] = {ORT_GEO_T};
-        for (int q = 0; q < 3; ++q) a.gthr[q] = gt[q] * m;
-    }
-    const int key_bits = bcost ? ort::kPathKeyBits + kHeavyKeyBits : ort::kPathKeyBits;
-    const size_t lds = lds_bytes(mode, ctx->depth, false);
-    const size_t lds_exact = lds_bytes(mode, ctx->depth, true);
-    const int pblocks = (mode == 0 && ctx->persistent) ? persistent_blocks(ctx->device, dcounters != nullptr, ctx->depth > 8, ctx->depth, lds, blocks) : 0;
-    hipError_t e;
-    const int fslot = (int)(ctx->frames % ort_ctx::kRing);  // this frame's timing slot
-    ctx->tseg[fslot] = 0;
-    // the frame's start: also the start of its first trace launch when that is timed (nothing is
-    // enqueued between them), which saves an event packet per frame (~1 % of a 1/8 band frame)
-    const bool no_times = (ctx->debug_flags & 1) || !ctx->launch_times;  // no per-launch events
-    const bool start_is_tr0 = maxd > 0 && !no_times;
-    ctx->ev0_last = start_is_tr0 ? ctx->tr0[fslot][0] : ctx->ev0;
-    HIPCHK(ctx, hipEventRecord(ctx->ev0_last, s));
-    for (int smp = 0; smp < ns; ++smp) {
-        a.sample = smp;
-        a.qlist = nullptr;  // bounce 0: every slot
-        a.qcount = nullptr;
-        // the alive paths of the current bounce in append order, and the buffer the next
-        // bounce's are appended to: qbuf[cur] / qcnt[cur] and qbuf[cur ^ 1] / qcnt[cur ^ 1]
-        int* qbuf[2] = {(int*)ctx->qlist.p, (int*)ctx->qlist2.p};
-        int* qcnt[2] = {(int*)ctx->qcount.p, (int*)ctx->qcount.p + 4};
-        int cur = 1;  // bounce 0 appends to qbuf[0]
-        const int bounces = maxd > 0 ? maxd : 1;
-        a.nobounce = maxd <= 0;
-        for (int b = 0; b < bounces; ++b) {
-            a.last = (b == bounces - 1);
-            const int fmode = fuse ? 1 : ((b == 0 && fuse_first) ? 2 : 0);
-            if (!a.nobounce) {
-                {   // this launch's counter set; mode 0 launches ort_trace_exact, which zeroes the other
-                    int* const set = (int*)ctx->defer_count.p + 16 * ctx->sync_set;
-                    a.sync = set;
-                    if (mode == 0) a.sync_next = (int*)ctx->defer_count.p + 16 * (ctx->sync_set ^ 1);
-                    else HIPCHK(ctx, hipMemsetAsync(set, 0, 64, s));
-                }
-                const int slot = fslot;
-                const int seg = ctx->tseg[slot];
-                // every trace launch of the frame, up to kSeg (analysis flag 1: none)
-                const bool timed = seg < ort_ctx::kSeg && !no_times;
-                if (timed && !ctx->tr0[slot][seg]) {
-                    HIPCHK(ctx, hipEventCreate(&ctx->tr0[slot][seg]));
-                    HIPCHK(ctx, hipEventCreate(&ctx->tr1[slot][seg]));
-                }
-                if (timed && !(seg == 0 && start_is_tr0)) HIPCHK(ctx, hipEventRecord(ctx->tr0[slot][seg], s));
-                const bool prim = b == 0;
-                const int pb = (pers_bounce && b > 0) ? pblocks : 0;
-                PipeArgs at = a;
-#if ORT_ANALYSIS
-                if (pb > 0 && a.wclock) {  // analysis (ORT_PERSIST_CLOCK): a record range per launch
-                    const long long nw = (long long)pb * (ctx->depth > 8 ? kPersistDeepBlock : kBlock) / 64 *
-                                         (ORT_PERSIST_STATS ? 2 : 1);  // records per launch
-                    at.wclock = (seg + 1) * nw <= ctx->wclock_n ? a.wclock + seg * nw : nullptr;
-                    at.wclock_n = (int)nw;
-                }
-#endif
-                if (fmode == 2) {  // the trace kernels append bounce 1's list (as ort_shade_kernel would)
-                    HIPCHK(ctx, hipMemsetAsync(qcnt[cur ^ 1], 0, sizeof(int), s));
-                    at.qnext = qbuf[cur ^ 1];
-                    at.qnext_count = qcnt[cur ^ 1];
-                    at.qnext_keys = listsort ? (uint32_t*)ctx->skeys.p : nullptr;
-                }
-                {   // heavy first: record index smp * bounces + b (bounces >= 1 only)
-                    const int hi = smp * bounces + b;
-                    if (bcost && pb > 0 && b > 0 && hi < nbc) at.bcost_w = bcost + (size_t)hi * slots;
-                    if (bcost_rd && fmode == 2 && hi + 1 < nbc && b + 1 < bounces) at.bcost_r = bcost_rd + (size_t)(hi + 1) * slots;
-                }
-                const bool do_split = split && (fmode == 1 || fmode == 2);
-                const unsigned long long fsig = do_split ? frame_sig(ctx, p, t) : 0ull;
-                if (do_split) {
-                    // the heavy rays of this frame (last frame's steps) -- listed by the scan the last
-                    // frame of this shape queued on the second stream, or by one here -- then their
-                    // split walks there, beside the per-tile kernel (which passes over them)
-                    const bool pre = ctx->pre_ok && ctx->pre_sig == fsig && ctx->pre_steps == split_steps &&
-                                     !(ctx->debug_flags & 2);
-                    ctx->pre_ok = false;
-                    int* hc = (int*)ctx->hcnt.p;
-                    // the second stream follows this one up to here: with shading fused (1 bounce)
-                    // nothing of this frame precedes the split walks on it but ev0 (event packets
-                    // cost the frame ~1 % each); bounce 0 of a longer path needs the list memset too
-                    if (fmode == 1) {
-                        HIPCHK(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->ev0_last, 0));
-                    } else {
-                        HIPCHK(ctx, hipEventRecord(ctx->ev_scan, s));
-                        HIPCHK(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->ev_scan, 0));
-                    }
-                    if (!pre) {  // (with pre, the last frame's exact kernel listed them, in this stream's order)
-                        HIPCHK(ctx, hipMemsetAsync(hc, 0, 64, ctx->aux_stream));
-                        ctx->hpar = 0;
-                        const HeavyScan H{(const uint16_t*)a.pcost, (int)slots, split_steps, ort_ctx::kSplitCap,
-                                          (uint32_t*)ctx->hbits.p, (int*)ctx->hlist.p, hc};
-                        hipLaunchKernelGGL(k_heavy_scan, dim3((unsigned)((slots + 4095) / 4096)), dim3(kBlock), 0,
-                                           ctx->aux_stream, H);
-                        HIPCHK(ctx, hipGetLastError());
-                        HIPCHK(ctx, hipEventRecord(ctx->ev_pre, ctx->aux_stream));
-                        HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_pre, 0));  // the tile kernel reads hbits
-                    }
-                    at.hsync = hc + 8 * ctx->hpar;
-                    at.hsync_next = hc + 8 * (ctx->hpar ^ 1);
-                    if ((e = launch_trace_split(ctx->depth > 8, fmode, at, lds, ctx->aux_stream)) != hipSuccess)
-                        return hip_fail(ctx, e, "hipGetLastError()");
-                    HIPCHK(ctx, hipEventRecord(ctx->ev_split, ctx->aux_stream));
-                    at.hbits = (const uint32_t*)ctx->hbits.p;
-                }
-                const int tblocks = (prim && pairs) ? (int)(blocks / 2) : (int)blocks;  // a workgroup per tile pair
-                e = launch_trace(dcounters != nullptr, mode, prim, at, tblocks, pb, lds, s, fmode);
-                if (e != hipSuccess) return hip_fail(ctx, e, "trace kernel launch");
-                if (do_split) {
-                    HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_split, 0));  // joined before the exact kernel
-                    if (timed) {
-                        HIPCHK(ctx, hipEventRecord(ctx->tr1[slot][seg], s));
-                        ctx->tseg[slot] = seg + 1;
-                    }
-                    // the exact kernel also lists the next frame's heavy rays, from this frame's
-                    // steps (final now) -- no scan launch or cross-stream wait opens the next frame;
-                    // ort_trace_split zeroed the other count pair
-                    ctx->hpar ^= 1;
-                    at.scan_pcost = a.pcost;
-                    at.scan_T = split_steps;
-                    at.scan_bits = (uint32_t*)ctx->hbits.p;
-                    at.scan_list = (int*)ctx->hlist.p;
-                    at.scan_count = (int*)ctx->hcnt.p + 8 * ctx->hpar;
-                    ctx->pre_sig = fsig;
-                    ctx->pre_steps = split_steps;
-                } else if (timed) {
-                    HIPCHK(ctx, hipEventRecord(ctx->tr1[slot][seg], s));
-                    ctx->tseg[slot] = seg + 1;
-                }
-                if (mode == 0) {
-                    e = launch_trace_exact(dcounters != nullptr, prim, fmode, at, lds_exact, s);
-                    if (e != hipSuccess) return hip_fail(ctx, e, "ort_trace_exact launch");
-                    ctx->sync_set ^= 1;  // it zeroes the other set for the next launch
-                    // it listed the next frame's heavy rays: only now may that frame skip its scan
-                    if (do_split) ctx->pre_ok = true;
-                }
-            }
-            if (!fuse && fmode != 2) {
-                // bounce >= 1: the bounce's alive paths in APPEND order (about slot order: the
-                // path-state reads and writes coalesce; the sorted trace list scattered them, C5
-                // 65.4 -> 63.0 ms) -- or, with the every-slot sort (sort_paths 1), every slot
-                PipeArgs a2 = a;
-                a2.qlist = nullptr;
-                a2.qcount = nullptr;
-                if (compact && !sorted && b > 0) {
-                    a2.qlist = qbuf[cur];
-                    a2.qcount = qcnt[cur];
-                }
-                if (compact && !sorted && !a.nobounce && b + 1 < bounces) {
-                    // the compaction: the shade kernel appends the paths that go on, one atomic
-                    // per workgroup (a separate rocprim::select pass over the slots cost 0.55 ms
-                    // per C5 bounce), into the other list buffer
-                    HIPCHK(ctx, hipMemsetAsync(qcnt[cur ^ 1], 0, sizeof(int), s));
-                    a2.qnext = qbuf[cur ^ 1];
-                    a2.qnext_count = qcnt[cur ^ 1];
-                    a2.qnext_keys = listsort ? (uint32_t*)ctx->skeys.p : nullptr;
-                    const int hn = smp * bounces + b + 1;  // the next bounce's record
-                    if (bcost_rd && hn < nbc) a2.bcost_r = bcost_rd + (size_t)hn * slots;
-                }
-                e = launch_shade(mode, b == 0, direct, a2, (int)blocks, s);
-                if (e != hipSuccess) return hip_fail(ctx, e, "ort_shade_kernel launch");
-            }
-            if (compact && !a.nobounce && b + 1 < bounces) {  // the next bounce walks only the alive paths
-                if (sorted) {
-                    const ort::SortBuffers sb{(uint32_t*)ctx->skeys.p, (uint32_t*)ctx->skeys2.p, (int*)ctx->svals.p,
-                                              (int*)ctx->qlist.p};
-                    e = ort::sortAlive(ctx->qtemp.p, qtemp_bytes, (const float4*)ctx->po.p, (const float4*)ctx->pd.p,
-                                       (int)slots, ctx->root_lo, ctx->root_hi, (const uint32_t*)ctx->key_spread.p, sb,
-                                       (int*)ctx->qcount.p, s);
-                    if (e != hipSuccess) return hip_fail(ctx, e, "path compaction");
-                }  // else the shade kernel appended them
-                if (sorted) {
-                    a.qlist = (const int*)ctx->qlist.p;
-                    a.qcount = (const int*)ctx->qcount.p;
-                } else {
-                    cur ^= 1;  // the list just appended is the next bounce's
-                    if (listsort) {
-                        // sort only about the alive paths, not every slot (C5: 36.6 M keys, not
-                        // 99.6 M), without reading the length back: the bound is this bounce's
-                        // length in an earlier frame of the same shape plus 1/64 + 1024 (the
-                        // same camera gives the same length), every slot when there is none
-                        const int hi = smp * bounces + b;
-                        long long bound = (long long)slots;
-                        if (ctx->sort_bound > 0) bound = ctx->sort_bound;
-                        else if (hi < ort_ctx::kHints) {
-                            const int h = ((volatile int*)ctx->alive_host)[ctx->hint_bank * ort_ctx::kHints + hi];
-                            if (h >= 0) bound = (long long)h + (h >> 6) + 1024;
-                        }
-                        bound = std::min<long long>(bound, (long long)slots);
-                        // (key, path) pairs as the shade / trace kernels appended them
-                        const ort::SortBuffers sb{(uint32_t*)ctx->skeys.p, (uint32_t*)ctx->skeys2.p, qbuf[cur],
-                                                  (int*)ctx->svals.p};
-                        e = ort::sortListBounded(ctx->qtemp.p, qtemp_bytes, (int)bound, qcnt[cur], sb, s, key_bits);
-                        if (e != hipSuccess) return hip_fail(ctx, e, "path list sort");
-                        if (hi < ort_ctx::kHints)  // the next frame's bound (pinned: no host wait)
-                            HIPCHK(ctx, hipMemcpyAsync(ctx->alive_host + ctx->hint_bank * ort_ctx::kHints + hi, qcnt[cur], sizeof(int),
-                                                       hipMemcpyDeviceToHost, s));
-                    }
-                    a.qlist = listsort ? (const int*)ctx->svals.p : qbuf[cur];
-                    a.qcount = qcnt[cur];
-                }
-            }
-        }
-    }
-    if (ctx->tseg[fslot] > 0) ctx->frames += 1;
-    if (listsort) {  // after this frame's hint copies: the bank is free once this completes
-        HIPCHK(ctx, hipEventRecord(ctx->hint_ev[ctx->hint_bank], s));
-        ctx->hint_ev_used[ctx->hint_bank] = true;
-    }
-    if (!direct && !a.final_out) {
-        hipLaunchKernelGGL(ort_finalize_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
-        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, "ort_finalize_kernel launch");
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, s));
-    ctx->timed = true;
-    ctx->sync_ok = true;  // every launch enqueued: the counter sets are in step again
-    return finish_output(ctx, o, dout, t, pitch, stream, s);
-}
-
-// One row per ranged option: the field it writes, its inclusive range, and what a value outside it
-// is answered with.  The options that are not a plain range are ort_set_option's own cases.
-struct OptionRow {
-    int id;
-    int ort_ctx::*field;
-    int lo, hi;
-    const char* bad;
-};
-const OptionRow kOptions[] = {
-    {ORT_OPT_FORCE_LAYOUT, &ort_ctx::force_layout, -1, ORT_LAYOUT_EXPLICIT, "bad layout"},
-    {ORT_OPT_KID_SKIP, &ort_ctx::kid_skip, 0, 2, "ORT_OPT_KID_SKIP: 0, 1 or 2"},
-    {ORT_OPT_XCD_SWIZZLE, &ort_ctx::xcd_swizzle, -1, 2, "xcd swizzle must be -1 (auto), 0, 1 or 2"},
-    {ORT_OPT_SORT_PATHS, &ort_ctx::sort_paths, 0, 2, "sort_paths must be 0, 1 or 2"},
-    {ORT_OPT_HEAVY_FIRST, &ort_ctx::heavy_first, 0, 65535, "ORT_OPT_HEAVY_FIRST: 0 (off) .. 65535 steps"},
-    {ORT_OPT_TILE_PAIRS, &ort_ctx::tile_pairs, -1, 1, "ORT_OPT_TILE_PAIRS: -1 (auto), 0 or 1"},
-    {ORT_OPT_SPLIT_HEAVY, &ort_ctx::split_steps, -1, 65535, "ORT_OPT_SPLIT_HEAVY: -1 (auto), 0 (off) .. 65535 steps"},
-    {ORT_OPT_SPLIT_LEVEL, &ort_ctx::split_level, 0, ORT_COMPACT_MAX_DEPTH, "ORT_OPT_SPLIT_LEVEL: 0 (auto) .. 10"},
-    {ORT_OPT_PIXEL_PATHS, &ort_ctx::pixel_paths, -1, 1, "ORT_OPT_PIXEL_PATHS: -1 (auto), 0 or 1"},
-    {ORT_OPT_PIXEL_SPECULATE, &ort_ctx::pixel_spec, -1, 1, "ORT_OPT_PIXEL_SPECULATE: -1 (auto), 0 or 1"},
-    {ORT_OPT_PIXEL_HEAVY_FIRST, &ort_ctx::pixel_heavy_first, -1, 1, "ORT_OPT_PIXEL_HEAVY_FIRST: -1 (auto), 0 or 1"},
-    {ORT_OPT_PIXEL_LDS_SCENE, &ort_ctx::pixel_lds_scene, 0, 1, "ORT_OPT_PIXEL_LDS_SCENE: 0 or 1"},
-    {ORT_OPT_LAUNCH_TIMES, &ort_ctx::launch_times, 0, 1, "ORT_OPT_LAUNCH_TIMES: 0 or 1"},
-#if ORT_ANALYSIS  // analysis: 1 no trace-timing events, 2 no queued heavy scan
-    {ORT_OPT_DEBUG_FLAGS, &ort_ctx::debug_flags, 0, 3, "ORT_OPT_DEBUG_FLAGS: 0 .. 3"},
-#endif
-    {ORT_OPT_HEAVY_PRIO, &ort_ctx::heavy_prio, 0, 65535, "ORT_OPT_HEAVY_PRIO: 0 (off) .. 65535 steps"},
-    {ORT_OPT_COST_ORDER, &ort_ctx::cost_order, 0, 1, "ORT_OPT_COST_ORDER: 0 or 1"},
-    {ORT_OPT_SORT_BOUND, &ort_ctx::sort_bound, 0, INT_MAX, "ORT_OPT_SORT_BOUND must be >= 0"},  // no upper bound
-    {ORT_OPT_REFILL, &ort_ctx::refill, 1, 64, "refill must be 1..64"},
-};
-
 }  // namespace
 
-extern "C" {
-
-int ort_create(int device, ort_ctx** out) {
-    if (!out) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_create: null out");
-    *out = nullptr;
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) return hip_fail(nullptr, e, "hipGetDeviceCount");
-    if (device < 0 || device >= n) {
-        std::string have;
-        [[clang::noinline]] have = std::to_string(n);  // (called, not inlined: the library keeps exporting its copy)
-        return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_create: device " + std::to_string(device) + " not present (" + have +
-                                                      " visible)");
-    }
-    ort_ctx* c = new (std::nothrow) ort_ctx();
-    if (!c) return fail(nullptr, ORT_ERR_OUT_OF_MEMORY, "ort_create: out of host memory");
-    c->device = device;
-    if ((e = hipSetDevice(device)) != hipSuccess || (e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess) {
-        const int rc = hip_fail(nullptr, e, "ort_create");
-        delete c;
-        return rc;
-    }
-    for (int i = 0; i < ort_ctx::kRing; ++i) {
-        if ((e = hipEventCreate(&c->tr0[i][0])) != hipSuccess || (e = hipEventCreate(&c->tr1[i][0])) != hipSuccess) {
-            const int rc = hip_fail(nullptr, e, "ort_create: events");
-            ort_destroy(c);
-            return rc;
-        }
-    }
-    if ((e = hipHostMalloc((void**)&c->alive_host, sizeof(int) * ort_ctx::kHints * ort_ctx::kHintBanks,
-                           hipHostMallocDefault)) != hipSuccess) {
-        c->alive_host = nullptr;
-        const int rc = hip_fail(nullptr, e, "ort_create: pinned hint buffer");
-        ort_destroy(c);
-        return rc;
-    }
-    for (int i = 0; i < ort_ctx::kHints * ort_ctx::kHintBanks; ++i) c->alive_host[i] = -1;
-    for (int i = 0; i < ort_ctx::kHintBanks; ++i)
-        if ((e = hipEventCreateWithFlags(&c->hint_ev[i], hipEventDisableTiming)) != hipSuccess) {
-            const int rc = hip_fail(nullptr, e, "ort_create: hint events");
-            ort_destroy(c);
-            return rc;
-        }
-    // (the second stream itself is created with the first split frame: a stream takes one of the
-    // process's few hardware queues, and contexts that never split -- group ranks sharing a
-    // device -- should not crowd the others' queues)
-    if ((e = hipEventCreateWithFlags(&c->ev_scan, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&c->ev_split, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&c->ev_pre, hipEventDisableTiming)) != hipSuccess) {
-        const int rc = hip_fail(nullptr, e, "ort_create: second stream");
-        ort_destroy(c);
-        return rc;
-    }
-    *out = c;
-    return ORT_OK;
-}
-
-int ort_destroy(ort_ctx* ctx) {
-    if (!ctx) return ORT_OK;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (ort_accum* a : ctx->accums) free_accum(a);
-    ctx->accums.clear();
-    free_scene(ctx);
-    free_buf(ctx->scratch_out);
-    free_buf(ctx->counters);
-    DevBuf* pipe[] = {&ctx->hit, &ctx->defer_list, &ctx->defer_count, &ctx->po, &ctx->pd, &ctx->pc, &ctx->prng, &ctx->pcol,
-                      &ctx->qlist, &ctx->qlist2, &ctx->qcount, &ctx->qtemp, &ctx->skeys, &ctx->skeys2, &ctx->svals, &ctx->key_spread,
-                      &ctx->pcost, &ctx->bcost, &ctx->hbits, &ctx->hlist, &ctx->hcnt, &ctx->pplist, &ctx->ppcnt, &ctx->ppcost, &ctx->spst, &ctx->spcol, &ctx->spfix, &ctx->spfixn};
-    for (DevBuf* b : pipe) free_buf(*b);
-    free_query(ctx->query);
-    free_denoise(ctx->denoise);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    for (int i = 0; i < ort_ctx::kRing; ++i)
-        for (int j = 0; j < ort_ctx::kSeg; ++j) {
-            if (ctx->tr0[i][j]) (void)hipEventDestroy(ctx->tr0[i][j]);
-            if (ctx->tr1[i][j]) (void)hipEventDestroy(ctx->tr1[i][j]);
-        }
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    if (ctx->alive_host) (void)hipHostFree(ctx->alive_host);
-    for (hipEvent_t ev : ctx->hint_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (ctx->aux_stream) {
-        (void)hipStreamSynchronize(ctx->aux_stream);
-        (void)hipStreamDestroy(ctx->aux_stream);
-    }
-    if (ctx->ev_scan) (void)hipEventDestroy(ctx->ev_scan);
-    if (ctx->ev_split) (void)hipEventDestroy(ctx->ev_split);
-    if (ctx->ev_pre) (void)hipEventDestroy(ctx->ev_pre);
-    delete ctx;
-    return ORT_OK;
-}
-
-const char* ort_last_error(const ort_ctx* ctx) { return ctx ? ctx->err.c_str() : ort::thread_error(); }
-
-int ort_set_option(ort_ctx* ctx, int option, int value) {
-    if (!ctx) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_set_option: null ctx");
-    if (option == ORT_OPT_PERSISTENT) {
-        if (value == 1)  // removed in round 4
-            return fail(ctx, ORT_ERR_UNSUPPORTED, "ORT_OPT_PERSISTENT 1 (every trace persistent) was removed (C5 -19 %)");
-        if (value != 0 && value != 2) return fail(ctx, ORT_ERR_INVALID_ARG, "persistent must be 0 or 2");
-        ctx->persistent = value;
-        return ORT_OK;
-    }
-    if (option == ORT_OPT_EXACT_TRAVERSAL) {
-        ctx->exact_only = value ? 1 : 0;
-        return ORT_OK;
-    }
-    for (const OptionRow& r : kOptions)
-        if (r.id == option) {
-            if (value < r.lo || value > r.hi) return fail(ctx, ORT_ERR_INVALID_ARG, r.bad);
-            ctx->*r.field = value;
-            return ORT_OK;
-        }
-#if !ORT_ANALYSIS
-    if (option == ORT_OPT_DEBUG_FLAGS)
-        return fail(ctx, ORT_ERR_UNSUPPORTED, "ORT_OPT_DEBUG_FLAGS: analysis library only (libort_analysis.so)");
-#endif
-    if (ORT_OPT_IS_RETIRED(option))  // removed options
-        return fail(ctx, ORT_ERR_UNSUPPORTED, "option " + std::to_string(option) + " is retired (" +
-                                                  (option == 5 ? "packet walk" : option == 7 ? "wave queue"
-                                                                                             : "longest-first workgroups") +
-                                                  ": measured slower, DESIGN.md 4)");
-    return fail(ctx, ORT_ERR_INVALID_ARG, "unknown option");
-}
-
-int ort_upload_scene(ort_ctx* ctx, const float* cr, const float* ma, const float* fr, int32_t n_spheres,
-                     const float* node_min, const float* node_max, const int32_t* co, const int32_t* oo,
-                     const int32_t* cnt, int32_t n_nodes, const int32_t* idx, int64_t n_indices) {
-    if (!ctx) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_upload_scene: null ctx");
-    try {
-        ort::SceneInput in{cr, ma, fr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices};
-        return upload_impl(ctx, in);
-    } catch (const std::bad_alloc&) {
-        return fail(ctx, ORT_ERR_OUT_OF_MEMORY, "ort_upload_scene: out of host memory");
-    } catch (const std::exception& ex) {
-        return fail(ctx, ORT_ERR_INTERNAL, std::string("ort_upload_scene: ") + ex.what());
-    }
-}
-
-int ort_upload_octree_nodes(ort_ctx* ctx, const float* cr, const float* ma, const float* fr, int32_t n_spheres,
-                            const void* nodes, int32_t n_nodes, const int32_t* idx, int64_t n_indices) {
-    if (!ctx) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_upload_octree_nodes: null ctx");
-    if (n_nodes < 0 || (n_nodes > 0 && !nodes)) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_upload_octree_nodes: bad nodes");
-    try {
-        struct Rec { float mn[3], mx[3]; int32_t co, oo, cnt; };
-        static_assert(sizeof(Rec) == 36, "GPUOctreeNode layout");
-        const Rec* r = (const Rec*)nodes;
-        std::vector<float> mn(3 * (size_t)n_nodes), mx(3 * (size_t)n_nodes);
-        std::vector<int32_t> co((size_t)n_nodes), oo((size_t)n_nodes), cn((size_t)n_nodes);
-        for (int32_t i = 0; i < n_nodes; ++i) {
-            std::memcpy(&mn[3 * (size_t)i], r[i].mn, 12);
-            std::memcpy(&mx[3 * (size_t)i], r[i].mx, 12);
-            co[i] = r[i].co;
-            oo[i] = r[i].oo;
-            cn[i] = r[i].cnt;
-        }
-        ort::SceneInput in{cr, ma, fr, n_spheres, mn.data(), mx.data(), co.data(), oo.data(), cn.data(), n_nodes, idx, n_indices};
-        return upload_impl(ctx, in);
-    } catch (const std::bad_alloc&) {
-        return fail(ctx, ORT_ERR_OUT_OF_MEMORY, "ort_upload_octree_nodes: out of host memory");
-    } catch (const std::exception& ex) {
-        return fail(ctx, ORT_ERR_INTERNAL, std::string("ort_upload_octree_nodes: ") + ex.what());
-    }
-}
-
-int ort_scene_get_info(const ort_ctx* ctx, ort_scene_info* info) {
-    if (!ctx || !info) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_scene_get_info: null argument");
-    if (!ctx->has_scene) return fail(const_cast<ort_ctx*>(ctx), ORT_ERR_NO_SCENE, "no scene uploaded");
-    info->n_spheres = ctx->n_spheres;
-    info->n_nodes = ctx->n_nodes;
-    info->n_indices = ctx->n_indices;
-    info->layout = ctx->layout;
-    info->tree_depth = ctx->depth;
-    int64_t b = 0;
-    each_scene_buffer(*ctx, [&](const DevBuf& d) { b += (int64_t)d.bytes; });
-    info->device_bytes = b;
-    return ORT_OK;
-}
-
-int ort_build_scene(ort_ctx* ctx, const float* sphere_center_radius, const float* sphere_mat_albedo,
-                    const float* sphere_fuzz_ri, int32_t n_spheres, int32_t max_depth, int32_t max_spheres_per_node,
-                    int32_t keep_tree) {
-    if (!ctx) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_build_scene: null ctx");
-    try {
-        return build_impl(ctx, sphere_center_radius, sphere_mat_albedo, sphere_fuzz_ri, n_spheres, max_depth,
-                          max_spheres_per_node, keep_tree);
-    } catch (const std::exception& ex) {
-        return fail(ctx, ORT_ERR_INTERNAL, std::string("ort_build_scene: ") + ex.what());
-    }
-}
-
-int ort_scene_export_octree(ort_ctx* ctx, float* node_min, float* node_max, int32_t* children_offset,
-                            int32_t* objects_offset, int32_t* object_count, int32_t* object_indices) {
-    if (!ctx) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_scene_export_octree: null ctx");
-    const ort::GpuTree& t = ctx->tree;
-    if (!ctx->has_scene || !t.co)
-        return fail(ctx, ORT_ERR_NO_SCENE, "ort_scene_export_octree: no GPU-built tree kept (ort_build_scene keep_tree)");
-    if (!node_min || !node_max || !children_offset || !objects_offset || !object_count || (!object_indices && t.n_indices))
-        return fail(ctx, ORT_ERR_INVALID_ARG, "ort_scene_export_octree: null output");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)t.n_nodes;
-    HIPCHK(ctx, hipMemcpy(node_min, t.node_min, 12 * n, hipMemcpyDeviceToHost));
-    HIPCHK(ctx, hipMemcpy(node_max, t.node_max, 12 * n, hipMemcpyDeviceToHost));
-    HIPCHK(ctx, hipMemcpy(children_offset, t.co, 4 * n, hipMemcpyDeviceToHost));
-    HIPCHK(ctx, hipMemcpy(objects_offset, t.oo, 4 * n, hipMemcpyDeviceToHost));
-    HIPCHK(ctx, hipMemcpy(object_count, t.cnt, 4 * n, hipMemcpyDeviceToHost));
-    if (t.n_indices) HIPCHK(ctx, hipMemcpy(object_indices, t.idx, 4 * (size_t)t.n_indices, hipMemcpyDeviceToHost));
-    return ORT_OK;
-}
-
-int ort_get_stream(const ort_ctx* ctx, void** stream) {
-    if (!ctx || !stream) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_get_stream: null argument");
-    *stream = (void*)ctx->stream;
-    return ORT_OK;
-}
-
-int ort_last_build_ms(const ort_ctx* ctx, float* ms) {
-    if (!ctx || !ms) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_last_build_ms: null argument");
-    *ms = ctx->build_ms;
-    return ORT_OK;
-}
-
-int ort_render(ort_ctx* ctx, const ort_params* params, const ort_tile* tile, float* rgb_out, int out_is_device,
-               void* stream) {
-    const ort_output o = {rgb_out, out_is_device, ORT_FORMAT_RGB32F, ORT_PLACE_TILE, 0, 0};
-    return ort_render_ex(ctx, params, tile, &o, stream);
-}
-
-int ort_render_ex(ort_ctx* ctx, const ort_params* params, const ort_tile* tile, const ort_output* output,
-                  void* stream) {
-    if (!ctx) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_render: null ctx");
-    return render_impl(ctx, params, tile, output, stream, nullptr);
-}
-
-int ort_last_kernel_ms(ort_ctx* ctx, float* ms) {
-    if (!ctx || !ms) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_last_kernel_ms: null argument");
-    if (!ctx->timed) return fail(ctx, ORT_ERR_NO_SCENE, "no kernel launched yet");
-    HIPCHK(ctx, hipEventSynchronize(ctx->ev1));
-    HIPCHK(ctx, hipEventElapsedTime(ms, ctx->ev0_last, ctx->ev1));
-    return ORT_OK;
-}
-
-int ort_last_trace_ms(ort_ctx* ctx, float* ms) {
-    if (!ctx || !ms) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_last_trace_ms: null argument");
-    return ort_trace_times_ms(ctx, 1, ms) == 1 ? ORT_OK : fail(ctx, ORT_ERR_NO_SCENE, "no trace kernel timed yet");
-}
-
-int ort_trace_times_ms(ort_ctx* ctx, int n, float* ms) {
-    if (!ctx || !ms || n < 0) return -ORT_ERR_INVALID_ARG;
-    const long long have = std::min<long long>(ctx->frames, ort_ctx::kRing);
-    const int k = (int)std::min<long long>(n, have);
-    for (int i = 0; i < k; ++i) {
-        const int slot = (int)((ctx->frames - k + i) % ort_ctx::kRing);
-        if (hipEventSynchronize(ctx->tr1[slot][0]) != hipSuccess ||
-            hipEventElapsedTime(&ms[i], ctx->tr0[slot][0], ctx->tr1[slot][0]) != hipSuccess)
-            return -ORT_ERR_HIP;
-    }
-    return k;
-}
-
-int ort_frame_trace_times_ms(ort_ctx* ctx, int n, float* ms, int32_t* launches) {
-    if (!ctx || !ms || n < 0) return -ORT_ERR_INVALID_ARG;
-    const long long have = std::min<long long>(ctx->frames, ort_ctx::kRing);
-    const int k = (int)std::min<long long>(n, have);
-    for (int i = 0; i < k; ++i) {
-        const int slot = (int)((ctx->frames - k + i) % ort_ctx::kRing);
-        float sum = 0.0f;
-        for (int j = 0; j < ctx->tseg[slot]; ++j) {
-            float t = 0.0f;
-            if (hipEventSynchronize(ctx->tr1[slot][j]) != hipSuccess ||
-                hipEventElapsedTime(&t, ctx->tr0[slot][j], ctx->tr1[slot][j]) != hipSuccess)
-                return -ORT_ERR_HIP;
-            sum += t;
-        }
-        ms[i] = sum;
-        if (launches) launches[i] = ctx->tseg[slot];
-    }
-    return k;
-}
-
-int ort_count_traffic(ort_ctx* ctx, const ort_params* params, const ort_tile* tile, uint64_t* counts) {
-    if (!ctx || !counts) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_count_traffic: null argument");
-    const std::string bad = check_params(params, tile);  // before the counters and the frame are allocated
-    if (!bad.empty()) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_count_traffic: " + bad);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->counters.p) {
-        HIPCHK(ctx, hipMalloc(&ctx->counters.p, 64));
-        ctx->counters.bytes = 64;
-    }
-    HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
-    const size_t pix = tile ? (size_t)tile->width * (size_t)tile->rows : 0;
-    DevBuf tmp;
-    if (pix) HIPCHK(ctx, hipMalloc(&tmp.p, 12 * pix));
-    const ort_output o = {tmp.p, 1, ORT_FORMAT_RGB32F, ORT_PLACE_TILE, 0, 0};
-    const int rc = render_impl(ctx, params, tile, &o, nullptr, (unsigned long long*)ctx->counters.p);
-    if (rc == ORT_OK && !pix) {
-        // a tile of no pixels: render_impl launched nothing and waited for nothing, so the memset
-        // above may still be queued on the context's (non-blocking) stream, which the copy below
-        // does not wait for -- it would return the counters of the count before this one
-        for (int k = 0; k < ORT_COUNT_N; ++k) counts[k] = 0;
-        return ORT_OK;
-    }
-    if (rc == ORT_OK) {
-        unsigned long long h[8] = {0};
-        hipError_t e = hipMemcpy(h, ctx->counters.p, 64, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free_buf(tmp); return hip_fail(ctx, e, "ort_count_traffic: copy counters"); }
-        for (int k = 0; k < ORT_COUNT_N; ++k) counts[k] = h[k];
-        // pixels inside the frame (main() runs once per fragment)
-        const TileMap tm = {tile->x0, tile->width, tile->y0, tile->rows, tile->band_height, tile->band_stride};
-        uint64_t px = 0;
-        for (int j = 0; j < tile->rows; ++j)
-            if (tile_row_to_y(tm, j) < params->height) px += (uint64_t)tile->width;
-        counts[ORT_COUNT_PIXELS] = px;
-    }
-    free_buf(tmp);
-    return rc;
-}
-
-}  // extern "C"
+// The host half, in the one translation unit (a kernel template is emitted where it is first
+// named, so the order of these includes, host_launch.inc's dispatchers above all, is the code
+// object's): the context and its state, the scene, the dispatchers, the two render paths.
+#include "host_context.inc"
+#include "host_scene.inc"
+#include "host_launch.inc"
+#include "host_frame.inc"
+#include "host_pixel_paths.inc"
+#include "host_pipeline.inc"
 
 // The test-only host emulation (ort_debug_*): the analysis library only (libort_analysis.so).
 #if ORT_ANALYSIS

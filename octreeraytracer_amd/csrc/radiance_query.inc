@@ -190,9 +190,9 @@ int radiance_impl(ort_ctx* ctx, const ort_radiance_query* q, void* stream) {
                                            q->flags, q->reserved, q->on_device == 0);
     if (!bad.empty()) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_trace_radiance: " + bad);
     // the walk, as accum_mode picks it: the whole-pixel walk exists for the compact layout and brute force
-    if (!ctx->has_scene) return fail(ctx, ORT_ERR_NO_SCENE, "ort_trace_radiance: no scene uploaded");
-    const int mode = (q->use_octree == 1) ? (ctx->layout == ORT_LAYOUT_COMPACT ? 0 : 1) : 2;
-    if (mode != 2 && ctx->n_nodes <= 0) return fail(ctx, ORT_ERR_NO_SCENE, "ort_trace_radiance: scene has no octree");
+    if (!ctx->scene.has_scene) return fail(ctx, ORT_ERR_NO_SCENE, "ort_trace_radiance: no scene uploaded");
+    const int mode = (q->use_octree == 1) ? (ctx->scene.layout == ORT_LAYOUT_COMPACT ? 0 : 1) : 2;
+    if (mode != 2 && ctx->scene.n_nodes <= 0) return fail(ctx, ORT_ERR_NO_SCENE, "ort_trace_radiance: scene has no octree");
     if (mode == 1)
         return fail(ctx, ORT_ERR_UNSUPPORTED, "ort_trace_radiance: use_octree = 1 on the explicit layout (radiance queries "
                                               "take the whole-pixel walk: compact layout or brute force)");
@@ -224,7 +224,7 @@ int radiance_impl(ort_ctx* ctx, const ort_radiance_query* q, void* stream) {
     a.qlist = qa.qlist;
     bool lds_scene;
     const size_t lds = pixel_paths_lds(ctx, c.mode, a.P, lds_scene);
-    const int variant = c.mode == 2 ? 0 : (ctx->depth > 8 ? 1 : (lds_scene ? 2 : 3));
+    const int variant = c.mode == 2 ? 0 : (ctx->scene.depth > 8 ? 1 : (lds_scene ? 2 : 3));
     pick<0, 1, 2, 3>(variant, [&](auto V) {
         constexpr int MODE = ORT_V(V) == 0 ? 2 : 0;
         constexpr bool DEEP = ORT_V(V) == 1, LDS = ORT_V(V) == 2;
@@ -234,8 +234,7 @@ int radiance_impl(ort_ctx* ctx, const ort_radiance_query* q, void* stream) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(ctx, e, "ort_radiance_paths launch");
     // query_finish with this call's arrays: the second event, the copies back, the wait
-    HIPCHK(ctx, hipEventRecord(qs.ev1, c.s));
-    qs.timed = true;
+    HIPCHK(ctx, qs.ev.end(c.s));
     if (c.host) {
         HIPCHK(ctx, hipMemcpyAsync(q->radiance, qs.radiance.p, 12 * n, hipMemcpyDeviceToHost, c.s));
         if (q->states_out) HIPCHK(ctx, hipMemcpyAsync(q->states_out, qs.states.p, 8 * n, hipMemcpyDeviceToHost, c.s));

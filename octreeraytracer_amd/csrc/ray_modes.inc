@@ -101,7 +101,7 @@ int query_mode_impl(ort_ctx* ctx, const ort_ray_query_ex* qx, void* stream) {
     if ((rc = query_start(ctx, c, a.q))) return rc;
     const dim3 block(kBlock);
     if (c.mode == 0) {
-        const size_t lds = lds_bytes(0, ctx->depth, false);
+        const size_t lds = lds_bytes(0, ctx->scene.depth, false);
         pick<ORT_QM_NEAREST, ORT_QM_ANY>(qx->mode == ORT_QUERY_NEAREST ? ORT_QM_NEAREST : ORT_QM_ANY, [&](auto QM) {
             const int g = resident_blocks(ctx->device, ort_query_mode_tree<ORT_V(QM)>, kBlock, lds, c.blocks);
             hipLaunchKernelGGL((ort_query_mode_tree<ORT_V(QM)>), dim3(g), block, lds, c.s, a);

@@ -245,20 +245,6 @@ __global__ void __launch_bounds__(kBlock) k_query_keys(QueryArgs A, ort::MortonP
 
 constexpr long long kQueryMaxRays = 1ll << 30;
 
-// The scene's origin-code tables (path_key.h), built once per root box (shared with the path sort:
-// scene state, not frame state).
-int ensure_key_spread(ort_ctx* ctx) {
-    const float box[6] = {ctx->root_lo[0], ctx->root_lo[1], ctx->root_lo[2], ctx->root_hi[0], ctx->root_hi[1], ctx->root_hi[2]};
-    if (ctx->key_spread.p && std::memcmp(box, ctx->spread_box, sizeof box) == 0) return ORT_OK;
-    int rc;
-    if ((rc = ensure(ctx, ctx->key_spread, 4 * (size_t)ort::kSpreadWords))) return rc;
-    std::vector<uint32_t> tab((size_t)ort::kSpreadWords);
-    ort::mortonSpread(ort::mortonPlan(ctx->root_lo, ctx->root_hi), tab.data());
-    HIPCHK(ctx, hipMemcpy(ctx->key_spread.p, tab.data(), 4 * tab.size(), hipMemcpyHostToDevice));
-    std::memcpy(ctx->spread_box, box, sizeof box);
-    return ORT_OK;
-}
-
 std::string check_query(const ort_ray_query* q) {
     if (!q) return "null query";
     if (q->n_rays < 0 || q->n_rays > kQueryMaxRays) return "n_rays must be 0 .. 2^30";
@@ -299,9 +285,9 @@ int query_begin(ort_ctx* ctx, const char* who, bool walk, int use_octree, size_t
     c = QueryCall{};
     c.mode = 2;
     if (walk) {
-        if (!ctx->has_scene) return fail(ctx, ORT_ERR_NO_SCENE, std::string(who) + ": no scene uploaded");
-        c.mode = (use_octree == 1) ? (ctx->layout == ORT_LAYOUT_COMPACT ? 0 : 1) : 2;
-        if (c.mode != 2 && ctx->n_nodes <= 0) return fail(ctx, ORT_ERR_NO_SCENE, std::string(who) + ": scene has no octree");
+        if (!ctx->scene.has_scene) return fail(ctx, ORT_ERR_NO_SCENE, std::string(who) + ": no scene uploaded");
+        c.mode = (use_octree == 1) ? (ctx->scene.layout == ORT_LAYOUT_COMPACT ? 0 : 1) : 2;
+        if (c.mode != 2 && ctx->scene.n_nodes <= 0) return fail(ctx, ORT_ERR_NO_SCENE, std::string(who) + ": scene has no octree");
     }
     if (n == 0) return ORT_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -323,8 +309,7 @@ int query_begin(ort_ctx* ctx, const char* who, bool walk, int use_octree, size_t
                    (rc = ensure(ctx, q.list, 4 * n)) ||
                    (rc = ensure(ctx, q.temp, std::max<size_t>(ort::sortAliveTempBytes((int)n), 16))) || (rc = ensure_key_spread(ctx))))
         return rc;
-    if (!q.ev0) HIPCHK(ctx, hipEventCreate(&q.ev0));
-    if (!q.ev1) HIPCHK(ctx, hipEventCreate(&q.ev1));
+    HIPCHK(ctx, q.ev.create());
     std::memset(&a, 0, sizeof(a));
     if (walk) {
         a.S = device_scene(ctx);
@@ -335,8 +320,8 @@ int query_begin(ort_ctx* ctx, const char* who, bool walk, int use_octree, size_t
     a.rays = io.rays_in ? (c.host ? (const float*)q.rays.p : (const float*)io.rays_in) : nullptr;
     a.sync = (int*)q.sync.p;
     a.n = (int)n;
-    a.refill = ctx->refill;
-    a.exact_only = ctx->exact_only || !ctx->ordered;
+    a.refill = ctx->opt.refill;
+    a.exact_only = ctx->opt.exact_only || !ctx->scene.ordered;
     if (c.host && io.rays_in) HIPCHK(ctx, hipMemcpyAsync(q.rays.p, io.rays_in, sizeof(ort_ray) * n, hipMemcpyHostToDevice, c.s));
     c.n = n;
     return ORT_OK;
@@ -348,7 +333,7 @@ int query_sort(ort_ctx* ctx, const QueryCall& c, QueryArgs& a) {
     QueryState& q = ctx->query;
     hipError_t e;
     hipLaunchKernelGGL(k_query_keys, dim3((unsigned)std::min<long long>(c.blocks, 2048)), dim3(kBlock), 0, c.s, a,
-                       ort::mortonPlan(ctx->root_lo, ctx->root_hi), (const uint32_t*)ctx->key_spread.p, (uint32_t*)q.keys.p,
+                       ort::mortonPlan(ctx->scene.root_lo, ctx->scene.root_hi), (const uint32_t*)ctx->pipe.key_spread.p, (uint32_t*)q.keys.p,
                        (int*)q.vals.p);
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, "k_query_keys launch");
     const ort::SortBuffers sb = {(uint32_t*)q.keys.p, (uint32_t*)q.keys2.p, (int*)q.vals.p, (int*)q.list.p};
@@ -361,7 +346,7 @@ int query_sort(ort_ctx* ctx, const QueryCall& c, QueryArgs& a) {
 // After the entry point staged its own inputs: the counters' reset, the first timing event, the sort.
 int query_start(ort_ctx* ctx, const QueryCall& c, QueryArgs& a) {
     HIPCHK(ctx, hipMemsetAsync(ctx->query.sync.p, 0, 64, c.s));
-    HIPCHK(ctx, hipEventRecord(ctx->query.ev0, c.s));
+    HIPCHK(ctx, ctx->query.ev.begin(c.s));
     return c.sort ? query_sort(ctx, c, a) : ORT_OK;
 }
 
@@ -370,8 +355,7 @@ int query_start(ort_ctx* ctx, const QueryCall& c, QueryArgs& a) {
 int query_finish(ort_ctx* ctx, const QueryCall& c) {
     QueryState& q = ctx->query;
     const size_t n = c.n;
-    HIPCHK(ctx, hipEventRecord(q.ev1, c.s));
-    q.timed = true;
+    HIPCHK(ctx, q.ev.end(c.s));
     if (c.host) {
         if (c.io.rays_out) HIPCHK(ctx, hipMemcpyAsync(c.io.rays_out, q.rays.p, sizeof(ort_ray) * n, hipMemcpyDeviceToHost, c.s));
         if (c.io.hits) HIPCHK(ctx, hipMemcpyAsync(c.io.hits, q.hits.p, sizeof(ort_ray_hit) * n, hipMemcpyDeviceToHost, c.s));
@@ -386,14 +370,14 @@ int query_finish(ort_ctx* ctx, const QueryCall& c) {
 template <class Args>
 int launch_fast_walk(ort_ctx* ctx, const QueryCall& c, const Args& a, void (*deep_k)(Args), void (*flat_k)(Args),
                      void (*exact_k)(Args), const char* family) {
-    const bool deep = ctx->depth > 8;
+    const bool deep = ctx->scene.depth > 8;
     const int nb = deep ? kPersistDeepBlock : kBlock;
-    const size_t lds = deep ? lds_bytes(0, ctx->depth, false, kRevBounce, kPersistDeepBlock) : lds_bytes(0, ctx->depth, false);
+    const size_t lds = deep ? lds_bytes(0, ctx->scene.depth, false, kRevBounce, kPersistDeepBlock) : lds_bytes(0, ctx->scene.depth, false);
     void (*const rays_k)(Args) = deep ? deep_k : flat_k;
     hipError_t e;
     hipLaunchKernelGGL(rays_k, dim3(resident_blocks(ctx->device, rays_k, nb, lds, c.blocks)), dim3(nb), lds, c.s, a);
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, (std::string(family) + "_rays launch").c_str());
-    hipLaunchKernelGGL(exact_k, dim3((unsigned)std::min<long long>(c.blocks, 256)), dim3(kBlock), lds_bytes(0, ctx->depth, true),
+    hipLaunchKernelGGL(exact_k, dim3((unsigned)std::min<long long>(c.blocks, 256)), dim3(kBlock), lds_bytes(0, ctx->scene.depth, true),
                        c.s, a);
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, (std::string(family) + "_exact launch").c_str());
     return ORT_OK;
@@ -493,9 +477,8 @@ int ort_trace_rays(ort_ctx* ctx, const ort_ray_query* q, void* stream) {
 
 int ort_last_query_ms(ort_ctx* ctx, float* ms) {
     if (!ctx || !ms) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_last_query_ms: null argument");
-    if (!ctx->query.timed) return fail(ctx, ORT_ERR_NO_SCENE, "no query launched yet");
-    HIPCHK(ctx, hipEventSynchronize(ctx->query.ev1));
-    HIPCHK(ctx, hipEventElapsedTime(ms, ctx->query.ev0, ctx->query.ev1));
+    if (!ctx->query.ev.timed) return fail(ctx, ORT_ERR_NO_SCENE, "no query launched yet");
+    HIPCHK(ctx, ctx->query.ev.elapsed(ms));
     return ORT_OK;
 }
 
