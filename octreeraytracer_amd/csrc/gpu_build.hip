@@ -37,9 +37,6 @@ namespace {
 
 constexpr int kB = 256;
 
-__device__ __forceinline__ float gmin(float x, float y) { return (y < x) ? y : x; }  // glm::min
-__device__ __forceinline__ float gmax(float x, float y) { return (x < y) ? y : x; }  // glm::max
-
 // Octree::sphereIntersectsBox (src/octree.cpp:231-242): std::max(lo, std::min(c, hi)) per
 // axis, glm::dot((closest - c), (closest - c)) <= r*r.
 __device__ __forceinline__ bool sphere_box(float4 s, const float* lo, const float* hi) {
@@ -71,41 +68,71 @@ __device__ __forceinline__ bool subdivides(int32_t count, int depth, int maxDept
     return depth < maxDepth && (unsigned long long)(uint32_t)count > mspn;  // :191, size_t compare
 }
 
-// Root box partials: every thread folds its spheres starting from sphere 0's box (like :54-63).
-__global__ void k_bounds(const float4* sp, int n, float* part) {
+// The reference folds the spheres in index order and keeps the first of equal bounds, which shows
+// where they are -0 and +0.  A partial result therefore carries the index of the sphere it came
+// from: of two partials, merge_min / merge_max take the one the sequential fold would have kept,
+// the lower index among equal values, in whatever order the partials meet.  (A NaN bound of
+// sphere 0 is every partial's value and wins no comparison, so it stays; one of a later sphere
+// never enters a partial: as the sequential fold.)
+__device__ __forceinline__ void merge_min(float& v, int& i, float w, int k) {
+    if (w < v || (w == v && k < i)) {  // glm::min(v, w) = (w < v) ? w : v
+        v = w;
+        i = k;
+    }
+}
+__device__ __forceinline__ void merge_max(float& v, int& i, float w, int k) {
+    if (v < w || (w == v && k < i)) {  // glm::max(v, w) = (v < w) ? w : v
+        v = w;
+        i = k;
+    }
+}
+
+// Root box partials: every thread folds its spheres, in ascending order, starting from sphere 0's
+// box (like :54-63).
+__global__ void k_bounds(const float4* sp, int n, float* part, int* parti) {
     __shared__ float sh[6][kB];
+    __shared__ int si[6][kB];
     const float4 s0 = sp[0];
     float v[6] = {s0.x - s0.w, s0.y - s0.w, s0.z - s0.w, s0.x + s0.w, s0.y + s0.w, s0.z + s0.w};
+    int vi[6] = {0, 0, 0, 0, 0, 0};
     for (int i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB) {
         const float4 s = sp[i];
-        v[0] = gmin(v[0], s.x - s.w);
-        v[1] = gmin(v[1], s.y - s.w);
-        v[2] = gmin(v[2], s.z - s.w);
-        v[3] = gmax(v[3], s.x + s.w);
-        v[4] = gmax(v[4], s.y + s.w);
-        v[5] = gmax(v[5], s.z + s.w);
+        const float b[6] = {s.x - s.w, s.y - s.w, s.z - s.w, s.x + s.w, s.y + s.w, s.z + s.w};
+        for (int j = 0; j < 3; ++j) merge_min(v[j], vi[j], b[j], i);
+        for (int j = 3; j < 6; ++j) merge_max(v[j], vi[j], b[j], i);
     }
-    for (int j = 0; j < 6; ++j) sh[j][threadIdx.x] = v[j];
+    for (int j = 0; j < 6; ++j) {
+        sh[j][threadIdx.x] = v[j];
+        si[j][threadIdx.x] = vi[j];
+    }
     __syncthreads();
     for (int w = kB / 2; w > 0; w >>= 1) {
         if ((int)threadIdx.x < w) {
-            for (int j = 0; j < 3; ++j) sh[j][threadIdx.x] = gmin(sh[j][threadIdx.x], sh[j][threadIdx.x + w]);
-            for (int j = 3; j < 6; ++j) sh[j][threadIdx.x] = gmax(sh[j][threadIdx.x], sh[j][threadIdx.x + w]);
+            const int t = threadIdx.x;
+            for (int j = 0; j < 3; ++j) merge_min(sh[j][t], si[j][t], sh[j][t + w], si[j][t + w]);
+            for (int j = 3; j < 6; ++j) merge_max(sh[j][t], si[j][t], sh[j][t + w], si[j][t + w]);
         }
         __syncthreads();
     }
     if (threadIdx.x == 0)
-        for (int j = 0; j < 6; ++j) part[6 * blockIdx.x + j] = sh[j][0];
+        for (int j = 0; j < 6; ++j) {
+            part[6 * blockIdx.x + j] = sh[j][0];
+            parti[6 * blockIdx.x + j] = si[j][0];
+        }
 }
 
 // Final fold of the partials into the root record (node 0 of level 0).
-__global__ void k_root(const float* part, int nb, float* lmin, float* lmax, uint32_t* lcell) {
+__global__ void k_root(const float* part, const int* parti, int nb, float* lmin, float* lmax, uint32_t* lcell) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     float v[6];
-    for (int j = 0; j < 6; ++j) v[j] = part[j];
+    int vi[6];
+    for (int j = 0; j < 6; ++j) {
+        v[j] = part[j];
+        vi[j] = parti[j];
+    }
     for (int b = 1; b < nb; ++b) {
-        for (int j = 0; j < 3; ++j) v[j] = gmin(v[j], part[6 * b + j]);
-        for (int j = 3; j < 6; ++j) v[j] = gmax(v[j], part[6 * b + j]);
+        for (int j = 0; j < 3; ++j) merge_min(v[j], vi[j], part[6 * b + j], parti[6 * b + j]);
+        for (int j = 3; j < 6; ++j) merge_max(v[j], vi[j], part[6 * b + j], parti[6 * b + j]);
     }
     for (int j = 0; j < 3; ++j) {
         lmin[j] = v[j];
@@ -407,10 +434,12 @@ std::string gpuBuildOctree(const float4* sp, int32_t n, int32_t maxDepth, int32_
     if (!(err = alloc_level(levels[0], 1, sc)).empty()) return err;
     {
         const int nb = std::min(1024, grid_for(n));
-        float* part;
-        if (!(err = sc.get(part, 6 * (int64_t)nb)).empty()) return err;
-        hipLaunchKernelGGL(k_bounds, dim3(nb), dim3(kB), 0, s, sp, n, part);
-        hipLaunchKernelGGL(k_root, dim3(1), dim3(1), 0, s, part, nb, levels[0].nmin, levels[0].nmax, levels[0].cell);
+        float* part;  // 6 bounds a block, then the 6 sphere indices they came from
+        if (!(err = sc.get(part, 12 * (int64_t)nb)).empty()) return err;
+        int* parti = reinterpret_cast<int*>(part + 6 * (int64_t)nb);
+        hipLaunchKernelGGL(k_bounds, dim3(nb), dim3(kB), 0, s, sp, n, part, parti);
+        hipLaunchKernelGGL(k_root, dim3(1), dim3(1), 0, s, part, parti, nb, levels[0].nmin, levels[0].nmax,
+                           levels[0].cell);
         GB_CHK(hipGetLastError());
     }
     int* d_unordered;

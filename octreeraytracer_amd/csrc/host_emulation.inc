@@ -572,9 +572,14 @@ int64_t ort_debug_walk_steps(const float* cr, const float* ma, const float* fr, 
 }
 
 int ort_debug_lds_image(int32_t depth, const float* planes, uint32_t* image, int64_t cap_words, int32_t* layout) {
+    return ort_debug_lds_image_rev(depth, planes, 0, image, cap_words, layout);
+}
+
+int ort_debug_lds_image_rev(int32_t depth, const float* planes, int32_t rev_tables, uint32_t* image, int64_t cap_words,
+                            int32_t* layout) {
     if (depth < 0 || depth > ORT_COMPACT_MAX_DEPTH || !planes || !layout)
         return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_lds_image: bad argument");
-    const bool rev = ort::fast_rev_planes(depth);
+    const bool rev = rev_tables != 0 || ort::fast_rev_planes(depth);  // as k_lds_image
     const ort::LdsLayout l = ort::lds_layout(depth, rev);
     layout[0] = l.frames;
     layout[1] = l.lut;
@@ -629,6 +634,76 @@ int ort_debug_ctx_leaf16(ort_ctx* ctx, uint32_t* out, int64_t cap, int64_t* n) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, hipMemcpy(out, ctx->scene.leaf16.p, ctx->scene.leaf16.bytes, hipMemcpyDeviceToHost));
+    return ORT_OK;
+}
+
+// tests/layout_cases.py: one array of the compact layout HostScene::build holds for a tree, by name.
+int ort_debug_layout(const float* cr, int32_t n_spheres, const float* node_min, const float* node_max, const int32_t* co,
+                     const int32_t* oo, const int32_t* cnt, int32_t n_nodes, const int32_t* idx, int64_t n_indices,
+                     const char* name, void* out, int64_t cap_bytes, int64_t* bytes) {
+    try {
+        if (!name || !bytes) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_layout: null argument");
+        HostScene hs;
+        if (int rc = hs.build(cr, nullptr, nullptr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices,
+                              ORT_LAYOUT_COMPACT, 1, HostScene::kValidate))
+            return fail(nullptr, rc, hs.error);
+        const std::string what = name;
+        const int32_t depth = hs.cl.depth, ordered = hs.cl.ordered ? 1 : 0;
+        const void* src = nullptr;
+        size_t n = 0;
+        if (what == "node") src = hs.cl.node.data(), n = 4 * hs.cl.node.size();
+        else if (what == "kid") src = hs.cl.kid.data(), n = 4 * hs.cl.kid.size();
+        else if (what == "leaf_sph") src = hs.cl.leaf_sph.data(), n = 4 * hs.cl.leaf_sph.size();
+        else if (what == "leaf_idx") src = hs.cl.leaf_idx.data(), n = 4 * hs.cl.leaf_idx.size();
+        else if (what == "planes") src = hs.cl.planes.data(), n = 4 * hs.cl.planes.size();
+        else if (what == "leaf16") src = hs.leaf16.data(), n = 16 * hs.leaf16.size();
+        else if (what == "depth") src = &depth, n = 4;
+        else if (what == "ordered") src = &ordered, n = 4;
+        else return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_layout: unknown array " + what);
+        *bytes = (int64_t)n;
+        if (!out || n == 0) return ORT_OK;
+        if (cap_bytes < (int64_t)n) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_layout: out too small");
+        std::memcpy(out, src, n);
+        return ORT_OK;
+    } catch (const std::exception& ex) {
+        return fail(nullptr, ORT_ERR_INTERNAL, ex.what());
+    }
+}
+
+// tests/layout_cases.py: one device array of a context's scene, by name, copied to out; *bytes = its
+// size.  The scalars depth, ordered and layout come as one int32.
+int ort_debug_ctx_array(ort_ctx* ctx, const char* name, void* out, int64_t cap_bytes, int64_t* bytes) {
+    if (!ctx || !name || !bytes) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_debug_ctx_array: null argument");
+    if (!ctx->scene.has_scene) return fail(ctx, ORT_ERR_NO_SCENE, "ort_debug_ctx_array: no scene");
+    const std::string what = name;
+    const Scene& sc = ctx->scene;
+    const int32_t scalars[3] = {sc.depth, sc.ordered ? 1 : 0, sc.layout};
+    const char* const scalar_names[3] = {"depth", "ordered", "layout"};
+    for (int k = 0; k < 3; ++k)
+        if (what == scalar_names[k]) {
+            *bytes = 4;
+            if (!out) return ORT_OK;
+            if (cap_bytes < 4) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_debug_ctx_array: out too small");
+            std::memcpy(out, &scalars[k], 4);
+            return ORT_OK;
+        }
+    const DevBuf* b = nullptr;
+    if (what == "node") b = &sc.node;
+    else if (what == "kid") b = &sc.kid;
+    else if (what == "leaf_sph") b = &sc.leaf_sph;
+    else if (what == "leaf_idx") b = &sc.leaf_idx;
+    else if (what == "planes") b = &sc.planes;
+    else if (what == "nk") b = &sc.nk;
+    else if (what == "leaf16") b = &sc.leaf16;
+    else if (what == "lds_img") b = &sc.lds_img;
+    else if (what == "lds_rev") b = &sc.lds_rev;
+    else return fail(ctx, ORT_ERR_INVALID_ARG, "ort_debug_ctx_array: unknown array " + what);
+    *bytes = b->p ? (int64_t)b->bytes : 0;
+    if (!out || *bytes == 0) return ORT_OK;
+    if (cap_bytes < *bytes) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_debug_ctx_array: out too small");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(out, b->p, b->bytes, hipMemcpyDeviceToHost));
     return ORT_OK;
 }
 

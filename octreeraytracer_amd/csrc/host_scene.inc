@@ -11,6 +11,9 @@ int build_lds_image(ort_ctx* ctx) {
         const size_t bytes = (size_t)ort::lds_layout(ctx->scene.depth, rev || ort::fast_rev_planes(ctx->scene.depth)).frames;
         int rc;
         if ((rc = upload(ctx, img, nullptr, bytes))) return rc;
+        // k_lds_image writes the tables and the LUT; the words that pad the tables to 16 bytes are
+        // copied into LDS with the rest (never read there): zero, as the host's image has them
+        HIPCHK(ctx, hipMemsetAsync(img.p, 0, bytes, ctx->stream));
         hipLaunchKernelGGL(k_lds_image, dim3(1), dim3(kBlock), 0, ctx->stream, (const float*)ctx->scene.planes.p, ctx->scene.depth,
                            rev != 0, (unsigned char*)img.p);
         HIPCHK(ctx, hipGetLastError());

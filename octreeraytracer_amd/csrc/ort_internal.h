@@ -155,6 +155,21 @@ int ort_debug_leaf16(const float* sphere_center_radius, int32_t n_spheres, const
                      uint32_t* leaf_sph, uint32_t* leaf16, int64_t* sizes);
 // TEST-ONLY: a context's device leaf records (k_leaf16) copied to out[4 cap]; *n = their number.
 int ort_debug_ctx_leaf16(ort_ctx* ctx, uint32_t* out, int64_t cap, int64_t* n);
+// TEST-ONLY: ort_debug_lds_image with the choice of tables explicit: rev_tables != 0 gives the
+// reversed-table image a depth 9-10 scene keeps beside the default one (lds_rev).
+int ort_debug_lds_image_rev(int32_t depth, const float* planes, int32_t rev_tables, uint32_t* image, int64_t cap_words,
+                            int32_t* layout);
+// TEST-ONLY: one array of the compact layout the host emulation builds for a tree, by name: "node",
+// "kid", "leaf_sph", "leaf_idx", "planes", "leaf16" (none for a tree deeper than 8), or the scalars
+// "depth" and "ordered" (one int32 each).  *bytes = its size; copied to out when given (cap_bytes).
+int ort_debug_layout(const float* sphere_center_radius, int32_t n_spheres, const float* node_min, const float* node_max,
+                     const int32_t* children_offset, const int32_t* objects_offset, const int32_t* object_count,
+                     int32_t n_nodes, const int32_t* object_indices, int64_t n_indices, const char* name, void* out,
+                     int64_t cap_bytes, int64_t* bytes);
+// TEST-ONLY: one device array of a context's scene, by name, copied to out after the context's stream
+// has drained: those of ort_debug_layout, "nk", "lds_img", "lds_rev" (0 bytes where the scene has
+// none), or the scalars "depth", "ordered", "layout" (one int32 each).  *bytes = its size.
+int ort_debug_ctx_array(ort_ctx* ctx, const char* name, void* out, int64_t cap_bytes, int64_t* bytes);
 // TEST-ONLY: sphere tests and accepted hits of the host's depth <= 8 camera walks per leaf record
 // form since the last reset: {inline tests, inline hits, list tests, list hits}.
 int ort_debug_leaf_forms(uint64_t* out4, int32_t reset);

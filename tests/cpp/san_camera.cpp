@@ -4,6 +4,7 @@
 // tile reaching past the frame, both kinds of ray, on the compact layout (depth 5 and the 96-bit
 // walk of depth 9), the explicit layout and brute force; a tiling must give the frame's records,
 // rows past the frame must be empty, and ort_trace_camera's argument errors must come back as codes.
+// Also the layout export hooks (ort_debug_layout, ort_debug_lds_image_rev) on the same two trees.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -70,6 +71,31 @@ void camera_case(const char* name, int32_t n, uint32_t seed, int depth, int per_
     std::vector<float> cr(4 * (size_t)n), ma(4 * (size_t)n), fr(4 * (size_t)n);
     check(ort_scene_random(n, seed, cr.data(), ma.data(), fr.data()) == ORT_OK, "ort_scene_random");
     const Tree t = build(cr, n, depth, per_node);
+    {  // the layout export hooks (tests/layout_cases.py): every array into a buffer of exactly its size
+        std::vector<uint32_t> planes;
+        int tree_depth = -1;
+        for (const char* what : {"node", "kid", "leaf_sph", "leaf_idx", "leaf16", "depth", "ordered", "planes"}) {
+            int64_t bytes = -1;
+            auto get = [&](void* out, int64_t cap) {
+                return ort_debug_layout(cr.data(), n, t.nmin.data(), t.nmax.data(), t.co.data(), t.oo.data(), t.cnt.data(),
+                                        (int32_t)t.n_nodes, t.idx.data(), t.n_indices, what, out, cap, &bytes);
+            };
+            check(get(nullptr, 0) == ORT_OK && bytes >= 0 && bytes % 4 == 0, what);
+            planes.assign((size_t)bytes / 4, 0u);
+            check(get(planes.data(), bytes) == ORT_OK, what);
+            if (bytes > 4) check(get(planes.data(), bytes - 1) == ORT_ERR_INVALID_ARG, "a buffer too small is refused");
+            if (!std::strcmp(what, "depth")) tree_depth = (int)planes[0];
+        }
+        check(tree_depth >= 0 && tree_depth <= depth && (int64_t)planes.size() == 3 * (((int64_t)1 << tree_depth) + 1),
+              "planes of the tree's depth");
+        for (int rev = 0; rev < 2; ++rev) {
+            int32_t lay[7];
+            check(ort_debug_lds_image_rev(tree_depth, (const float*)planes.data(), rev, nullptr, 0, lay) == ORT_OK, "image size");
+            std::vector<uint32_t> img((size_t)lay[0] / 4);
+            check(ort_debug_lds_image_rev(tree_depth, (const float*)planes.data(), rev, img.data(), (int64_t)img.size(), lay) == ORT_OK,
+                  "LDS image");
+        }
+    }
     const int W = 37, H = 21;
     for (int which : {ORT_CAMERA_FIRST_SAMPLE, ORT_CAMERA_PIXEL_CENTRE}) {
         for (int mode = 0; mode < 3; ++mode) {  // compact, explicit, brute force

@@ -2,7 +2,13 @@
 REFERENCE builder: the committed fixtures and SHA-256 hashes tools/make_golden.py took from
 the reference's own src/octree.cpp (tests/golden/manifest.json), the host restatement
 (octree.cpp, itself pinned to those fixtures) for shapes the manifest does not hold, and the
-rendered frame against the CPU oracle."""
+rendered frame against the CPU oracle.  Builder edges against the host restatement, bit for bit:
+root bounds that are zero with both signs (the reference's sequential fold keeps the first of
+equal values; within a block, across blocks and across trips of k_bounds' grid-stride loop),
+sphere counts around a block of 256, and one renderer through builds and an upload.
+
+NaN or infinite sphere fields stay out of scope, as tests/chart_scenes.py already declares them:
+NaN payloads differ between x86 and the GPU, and the reference leaves the case undefined."""
 import hashlib
 import json
 from pathlib import Path
@@ -87,6 +93,93 @@ def test_gpu_builder_coincident_and_touching_spheres(ort, renderer):
     for d, m in ((3, 0), (5, 1), (8, 2)):
         renderer.build_scene(s, d, m, keep_tree=True)
         assert same_tree(renderer.export_octree(), ort.build_octree(s, d, m)), (d, m)
+
+
+NEG0, POS0 = 0x80000000, 0x00000000
+
+
+def zero_bounds(ort, n, at, side):
+    """n spheres whose root bound on x (side "min" or "max") is a zero of both signs: spheres at[0]
+    and at[1] give -0 and +0, in that order.  min: centre -0 radius 0 (-0 - 0 = -0) and centre 0.5
+    radius 0.5; max, mirrored: centre -0 radius -0 (-0 + -0 = -0) and centre -0.5 radius 0.5.  The
+    rest: the issue's sphere 0 of the trio, or random_spheres shifted so that no other bound on
+    that side reaches 0.  The reference's sequential fold keeps the zero of the lower index."""
+    sign = 1.0 if side == "min" else -1.0
+    if n == 3:
+        cr = np.array([(2 * sign, 2, 2, 1)] * 3, np.float32)
+    else:
+        cr = ort.random_spheres(n, 11).center_radius.copy()
+        bound = cr[:, 0] - sign * cr[:, 3]
+        cr[:, 0] += np.float32(2 * sign - (bound.min() if side == "min" else bound.max()))  # every bound beyond +-1
+    cr[at[0]] = (-0.0, 3, 3, 0.0 if side == "min" else -0.0)
+    cr[at[1]] = (0.5 * sign, 3, 3, 0.5)
+    s = ort.SphereSet.empty(n)
+    s.center_radius[:] = cr
+    s.mat_albedo[:, 1:] = 0.5
+    s.fuzz_ri[:, 1] = 1.5
+    return s
+
+
+# (spheres, indices of the -0 and the +0 bound, depth limit, maxSpheresPerNode): the trio and its
+# order-swapped variant; the zeros in different blocks of k_bounds; the -0 bound in lane 0 of block
+# 0's second trip of the grid-stride loop (1024 blocks of 256), the +0 bound in its first
+ZERO_CASES = [(3, (1, 2), 2, 0), (3, (2, 1), 2, 0), (300, (10, 290), 2, 0), (300, (290, 10), 2, 0),
+              (262_145, (262_144, 5), 1, 0)]
+
+
+@pytest.mark.parametrize("side", ["min", "max"])
+@pytest.mark.parametrize("n,at,d,m", ZERO_CASES, ids=["trio", "trio_swapped", "two_blocks", "two_blocks_swapped",
+                                                      "second_trip"])
+def test_gpu_builder_signed_zero_root_bounds(ort, renderer, n, at, d, m, side):
+    s = zero_bounds(ort, n, at, side)
+    host = ort.build_octree(s, d, m)
+    root = (host.node_min if side == "min" else host.node_max)[0, 0].view(np.uint32)
+    assert root == (NEG0 if at[0] < at[1] else POS0)  # the host tree: the zero of the lower index
+    renderer.build_scene(s, d, m, keep_tree=True)
+    t = renderer.export_octree()
+    got, want = t.gpu_records().view(np.uint32), host.gpu_records().view(np.uint32)
+    # on failure: (node, word of its 9, the device's, the host's) of the first records that differ
+    assert same_tree(t, host), [(int(i), int(w), hex(int(got[i, w])), hex(int(want[i, w])))
+                                for i, w in np.argwhere(got != want)[:6]]
+
+
+@pytest.mark.parametrize("n", [255, 256, 257])
+def test_gpu_builder_block_boundaries(ort, renderer, n):
+    """Sphere counts around one block of 256: the bounds' reduction, the pair lists and the scans."""
+    s = ort.random_spheres(n, 5)
+    renderer.build_scene(s, 3, 0, keep_tree=True)
+    assert same_tree(renderer.export_octree(), ort.build_octree(s, 3, 0))
+
+
+def test_gpu_builder_one_renderer_through_a_sequence(ort):
+    """Builds and an upload one after another in one context: every kept tree is the host's, info()
+    follows each step, and a tree that was not kept (or was replaced by an upload) is not exported."""
+    from layout_cases import Shape
+    big, small = ort.random_spheres(2000, 7), ort.random_spheres(3, 2)
+    up = ort.random_spheres(50, 3)
+    trees = {"big": ort.build_octree(big, 6, 0), "small": ort.build_octree(small, 0, 0), "up": ort.build_octree(up, 3, 1)}
+
+    def check_info(r, s, t):
+        i = r.info()
+        assert (i["n_spheres"], i["n_nodes"], i["n_indices"], i["tree_depth"], i["layout"]) == \
+               (s.n, t.n_nodes, t.n_indices, Shape(t).depth, "compact")
+
+    with ort.Renderer(0) as r:
+        for s, name, d, m in ((big, "big", 6, 0), (small, "small", 0, 0)):
+            r.build_scene(s, d, m, keep_tree=True)
+            assert same_tree(r.export_octree(), trees[name]), name
+            check_info(r, s, trees[name])
+        r.upload(up, trees["up"])
+        check_info(r, up, trees["up"])
+        with pytest.raises(ort.OrtError, match="no GPU-built tree kept"):
+            r.export_octree()
+        r.build_scene(big, 6, 0, keep_tree=True)
+        assert same_tree(r.export_octree(), trees["big"])
+        check_info(r, big, trees["big"])
+        r.build_scene(small, 0, 0, keep_tree=False)
+        check_info(r, small, trees["small"])
+        with pytest.raises(ort.OrtError, match="no GPU-built tree kept"):
+            r.export_octree()
 
 
 def test_gpu_built_scene_renders_like_the_oracle(ort, oracle, renderer, scene_c2):
