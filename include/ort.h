@@ -604,6 +604,41 @@ int ort_accum_last_pass_ms(ort_ctx* ctx, ort_accum* accum, float* ms);
 /* Frees the accumulation (NULL: ORT_OK); ort_destroy frees what is left. */
 int ort_accum_free(ort_ctx* ctx, ort_accum* accum);
 
+/* ---- luminance moments of an accumulation: how noisy is each pixel still? ----------------------
+ * ort_accum_begin_ex with ORT_ACCUM_MOMENTS begins an accumulation whose passes also keep, per path
+ * slot, m2: the sum of the squared luminances of the pixel's samples (24 bytes a slot instead of
+ * 20).  flags == 0 is ort_accum_begin exactly (state, device_bytes, kernels); unknown bits:
+ * ORT_ERR_INVALID_ARG.  In float32, one operation each, at the end of sample s of a pixel, after
+ * col += c (c the sample's radiance):
+ *     l = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;   m2 = m2 + l * l
+ * m2 starts at 0 with sample 0 (ort_accum_restart resets it with the colour sums).  The pictures a
+ * moments accumulation writes are the plain accumulation's bit for bit: the moments only add state.
+ * ort_accum_read_moments writes, for every tile pixel with k = samples_done:
+ *     mean     = col / (float)k per channel (k == 1: col itself): linear, no gamma -- the division
+ *                ort_accum_render's preview makes, so pow(mean, 1/2.2) is that preview bit for bit
+ *     L        = (0.2126f * mean.x + 0.7152f * mean.y) + 0.0722f * mean.z;   e2 = m2 / (float)k
+ *     variance = max(e2 - L * L, 0) / (float)(k - 1): the variance of the mean's luminance, in linear
+ *                units; -1.0f = no estimate: k < 2, or e2 or L is not finite
+ * mean works on any accumulation; variance needs ORT_ACCUM_MOMENTS.  Rows with y >= height get
+ * mean = 0 and variance = -1.  The tile mapping (index = output row j x tile->width + column),
+ * on_device, the stream rules and the staging of host pointers (buffers of the accumulation's own,
+ * counted in device_bytes) are ort_accum_render's.  The call traces nothing and neither reads nor
+ * writes render, query or other accumulations' state.  A tile of no pixels: ORT_OK, nothing written.
+ * ORT_ERR_INVALID_ARG, with the outputs untouched: NULL arguments, mean and variance both NULL,
+ * reserved != 0, pointers that are not 4-byte aligned, an accumulation of another context,
+ * samples_done == 0, variance on an accumulation without ORT_ACCUM_MOMENTS.  ORT_ERR_NO_SCENE after
+ * a scene change, as for a pass.  Not in scope: moments on an ort_group, in ort_render or in the
+ * per-bounce pipeline; sample counts driven by the variance. */
+#define ORT_ACCUM_MOMENTS 1   /* the passes keep m2, the sum of the samples' squared luminances */
+int ort_accum_begin_ex(ort_ctx* ctx, const ort_params* params, const ort_tile* tile, int32_t flags, ort_accum** out);
+typedef struct ort_accum_moments {
+    float* mean;       /* NULL, or 3 floats per tile pixel, tight, tile row j first: linear, no gamma */
+    float* variance;   /* NULL, or 1 float per tile pixel, tight */
+    int32_t on_device; /* != 0: both are device pointers on ctx's device */
+    int32_t reserved[3]; /* 0 */
+} ort_accum_moments;
+int ort_accum_read_moments(ort_ctx* ctx, ort_accum* accum, const ort_accum_moments* moments, void* stream);
+
 /* ---- several GPUs, one process --------------------------------------
  * The reference renders on one GL context; a caller of Raytracer::render() reaches the 8-GPU
  * configs through a group: one context per listed device (scene replicated), the frame cut
@@ -763,9 +798,9 @@ const char* ort_version(void);
  * outside 0 .. 7, a negative or NaN sigma, unknown flags, reserved != 0, pointers that are not
  * 4-byte aligned, a color_pitch_bytes that is not 0 or a multiple of 4 of at least 12 * width and
  * below 2^31, ORT_PLACE_FRAME, an output that ort_render_ex refuses, on_device disagreeing with
- * output->is_device.  Not in scope: variance-guided colour weights (they need a sum of squares in
- * the accumulation state), albedo demodulation, temporal reprojection, denoising on an ort_group,
- * banded tiles (their rows are not neighbours in the frame). */
+ * output->is_device.  Variance-guided weights for pictures of several samples: ort_denoise_ex.
+ * Not in scope: albedo demodulation, temporal reprojection, denoising on an ort_group, banded
+ * tiles (their rows are not neighbours in the frame). */
 #define ORT_DENOISE_SAME_SPHERE 1   /* a tap of another sphere id (a miss among them) adds nothing */
 typedef struct ort_denoise_desc {
     const float*       color;             /* RGB32F, row r at color + r * color_pitch_bytes */
@@ -785,6 +820,46 @@ int ort_denoise(ort_ctx* ctx, const ort_denoise_desc* d, const ort_output* outpu
  * host copies not), from HIP events on its stream.  Only valid once that stream has passed it.
  * ORT_ERR_INVALID_ARG: NULL arguments, or no ort_denoise has launched anything on ctx yet. */
 int ort_last_denoise_ms(ort_ctx* ctx, float* ms);
+
+/* ---- variance-guided denoising: the filter for a picture that refines while the camera rests ---
+ * ort_denoise_ex is ort_denoise with two optional additions: an SVGF-style edge-stopping term driven
+ * by a per-pixel variance of the luminance (ort_accum_read_moments'), propagated through the
+ * iterations, and a gamma on the output, so that the filter runs on linear radiance -- where the
+ * variance lives -- and still writes the display picture.  With variance == NULL and no
+ * ORT_DENOISE_GAMMA the call is ort_denoise bit for bit.  The term closes itself as the picture
+ * converges: one setting serves 2 and 64 samples per pixel.
+ * The arithmetic, float32, one operation each, in this order.  valid(x): x is finite and x >= 0.
+ * lum(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b.
+ *   prefilter (once, with the pack pass): for a pixel p with valid(v_p), var_p is the 3 x 3 binomial
+ *     mean of the valid in-image neighbours: k = k3[dy+1] * k3[dx+1], k3 = (1/4, 1/2, 1/4), dy = -1 .. 1
+ *     outside, dx = -1 .. 1 inside; ws += k; vs += k * v_q in that order; var_p = vs / ws.  Without a
+ *     valid v_p, var_p = v_p (no estimate).
+ *   iteration i, pixel p, tap q, after ort_denoise's terms and not for the taps that add nothing:
+ *     if valid(var_p): inv_v = 1 / ((sigma_variance * sigma_variance) * var_p + 1e-12f), once per pixel;
+ *         dl = lum(cur_p) - lum(cur_q);  wv = clamp01(1 - (dl * dl) * inv_v);  w = w * wv
+ *         sv += (w * w) * (valid(var_q) ? var_q : 0), in tap order, beside sw and sum
+ *     next_var_p = sv / (sw * sw) if valid(var_p), else var_p; a pixel copied through because its
+ *     colour is not finite keeps var_p.  Every iteration reads the previous iteration's variances.
+ *   A tap more than sigma_variance standard deviations away in luminance adds nothing; a converged
+ *   pixel (var_p == 0) only takes taps of its own luminance; without a valid var_p the term is off
+ *   for that pixel.
+ *   ORT_DENOISE_GAMMA: the last iteration's result, pixels copied through included, goes through
+ *     pow(x, 1/2.2) per channel (the render path's, glsl:659-661) before the RGB32F store or
+ *     ORT_FORMAT_RGBA8's quantiser.
+ * variance is rows * width floats, tight, a device pointer iff base.on_device; host pointers are
+ * staged through the denoiser's own grow-only buffers.  ORT_ERR_INVALID_ARG, output untouched:
+ * whatever ort_denoise refuses (base.flags may carry ORT_DENOISE_GAMMA here; ort_denoise still
+ * refuses it), variance with sigma_variance <= 0 or NaN, sigma_variance != 0 without variance, a
+ * variance that is not 4-byte aligned, reserved != 0.  ort_last_denoise_ms covers this call too.
+ * Not in scope: temporal reprojection, albedo demodulation, denoising on an ort_group. */
+#define ORT_DENOISE_GAMMA 2   /* the output is pow(result, 1/2.2) per channel, then the format */
+typedef struct ort_denoise_desc_ex {
+    ort_denoise_desc base;     /* base.flags may carry ORT_DENOISE_GAMMA here */
+    const float* variance;     /* NULL: term off.  Else rows * width floats, tight; device pointer iff base.on_device */
+    float sigma_variance;      /* > 0 with variance, 0 without */
+    int32_t reserved[3];       /* 0 */
+} ort_denoise_desc_ex;
+int ort_denoise_ex(ort_ctx* ctx, const ort_denoise_desc_ex* d, const ort_output* output, void* stream);
 
 #ifdef __cplusplus
 }

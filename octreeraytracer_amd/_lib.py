@@ -71,6 +71,7 @@ EXPORTED_SYMBOLS = (
     "ort_trace_rays_ex",
     "ort_trace_radiance",
     "ort_denoise", "ort_last_denoise_ms",
+    "ort_accum_begin_ex", "ort_accum_read_moments", "ort_denoise_ex",
 )
 ORT_GROUP_TRANSPORT_RCCL = 0
 ORT_GROUP_TRANSPORT_COPY = 1
@@ -98,6 +99,9 @@ ORT_RADIANCE_NORMALIZE = 2
 ORT_RADIANCE_GAMMA = 4
 # ort_denoise_desc.flags (ort_denoise)
 ORT_DENOISE_SAME_SPHERE = 1
+ORT_DENOISE_GAMMA = 2  # ort_denoise_ex only
+# ort_accum_begin_ex flags
+ORT_ACCUM_MOMENTS = 1
 
 
 class OrtParams(C.Structure):
@@ -165,6 +169,15 @@ class OrtDenoiseDesc(C.Structure):
     ]
 
 
+class OrtDenoiseDescEx(C.Structure):
+    _fields_ = [("base", OrtDenoiseDesc), ("variance", C.c_void_p), ("sigma_variance", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
+class OrtAccumMoments(C.Structure):
+    _fields_ = [("mean", C.c_void_p), ("variance", C.c_void_p), ("on_device", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class OrtSceneInfo(C.Structure):
     _fields_ = [
         ("n_spheres", C.c_int32), ("n_nodes", C.c_int32), ("n_indices", C.c_int64),
@@ -217,6 +230,14 @@ def _declare(lib, debug: str = "none"):
         "ort_denoise": (C.c_int, [_vp, C.POINTER(OrtDenoiseDesc), C.POINTER(OrtOutput), _vp]),
         "ort_last_denoise_ms": (C.c_int, [_vp, _fp]),
         "ort_debug_denoise": (C.c_int, [C.POINTER(OrtDenoiseDesc), C.POINTER(OrtOutput)]),
+        "ort_denoise_ex": (C.c_int, [_vp, C.POINTER(OrtDenoiseDescEx), C.POINTER(OrtOutput), _vp]),
+        "ort_debug_denoise_ex": (C.c_int, [C.POINTER(OrtDenoiseDescEx), C.POINTER(OrtOutput)]),
+        "ort_debug_gamma": (C.c_int, [_fp, C.c_int64, _fp]),
+        "ort_accum_begin_ex": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.c_int32, C.POINTER(_vp)]),
+        "ort_accum_read_moments": (C.c_int, [_vp, _vp, C.POINTER(OrtAccumMoments), _vp]),
+        "ort_debug_emulate_moments": (C.c_int, [_fp, _fp, _fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip,
+                                                C.c_int64, C.c_int32, C.POINTER(OrtParams), C.POINTER(OrtTile),
+                                                C.c_int32, _fp, _fp]),
         "ort_accum_begin": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(_vp)]),
         "ort_accum_render": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(OrtOutput), _vp]),
         "ort_accum_restart": (C.c_int, [_vp, _vp, C.POINTER(OrtParams)]),
@@ -285,7 +306,8 @@ def _declare(lib, debug: str = "none"):
         if name.startswith("ort_debug_") and (debug == "none" or (debug == "present" and not hasattr(lib, name))):
             continue
         if name in ("ort_trace_camera", "ort_trace_rays_ex", "ort_trace_radiance", "ort_denoise",
-                    "ort_last_denoise_ms") and debug == "present" and not hasattr(lib, name):
+                    "ort_last_denoise_ms", "ort_accum_begin_ex", "ort_accum_read_moments",
+                    "ort_denoise_ex") and debug == "present" and not hasattr(lib, name):
             continue  # an ORT_LIB override of a build from before these calls (A/B runs): calling it raises
         f = getattr(lib, name)
         f.restype = res

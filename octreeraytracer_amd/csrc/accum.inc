@@ -40,6 +40,11 @@ hipError_t launch_accum_paths(int device, int mode, bool deep, bool lds_scene, s
     return hipGetLastError();
 }
 
+// The same launch for an accumulation that keeps moments: ort_pixel_paths<..., 4>, named in
+// accum_moments.inc so that those kernels follow every other one.
+hipError_t launch_accum_moments_paths(int device, int mode, bool deep, bool lds_scene, size_t lds, long long needed,
+                                      const PipeArgs& a, hipStream_t s);
+
 // The walk an accumulation of params p takes on ctx's scene (0 compact, 2 brute force), or the
 // refusal: what the whole-pixel kernel does not exist for.
 int accum_mode(ort_ctx* ctx, const ort_params* p, const char* call, int& mode) {
@@ -58,8 +63,9 @@ bool accum_known(const ort_ctx* ctx, const ort_accum* acc) {
     return acc->ctx == ctx && std::find(ctx->accums.begin(), ctx->accums.end(), acc) != ctx->accums.end();
 }
 
-int accum_begin_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, ort_accum** out) {
+int accum_begin_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int flags, ort_accum** out) {
     *out = nullptr;
+    if (flags & ~ORT_ACCUM_MOMENTS) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_accum_begin_ex: unknown flag bits");
     const std::string bad = check_params(p, t);
     if (!bad.empty()) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_accum_begin: " + bad);
     int mode = 0, rc;
@@ -73,11 +79,12 @@ int accum_begin_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, ort_a
     acc->p = *p;
     acc->t = *t;
     acc->mode = mode;
+    acc->moments = (flags & ORT_ACCUM_MOMENTS) != 0;
     acc->blocks = blocks;
     acc->scene_gen = ctx->scene.scene_gen;
     const size_t slots = (size_t)blocks * kBlock;
     hipError_t e = hipSuccess;
-    if ((rc = ensure(ctx, acc->state, std::max<size_t>(20 * slots, 16))) || (rc = ensure(ctx, acc->sync, 64)) ||
+    if ((rc = ensure(ctx, acc->state, std::max<size_t>((acc->moments ? 24 : 20) * slots, 16))) || (rc = ensure(ctx, acc->sync, 64)) ||
         (e = acc->ev.create()) != hipSuccess) {
         if (!rc) rc = hip_fail(ctx, e, "ort_accum_begin: events");
         free_accum(acc);
@@ -157,7 +164,8 @@ int accum_render_impl(ort_ctx* ctx, ort_accum* acc, int n_samples, const ort_out
         HIPCHK(ctx, hipMemsetAsync(acc->sync.p, 0, 64, s));
         bool lds_scene;
         const size_t lds = pixel_paths_lds(ctx, acc->mode, a, lds_scene);
-        const hipError_t e = launch_accum_paths(ctx->device, acc->mode, ctx->scene.depth > 8, lds_scene, lds, acc->blocks, a, s);
+        const hipError_t e = (acc->moments ? launch_accum_moments_paths : launch_accum_paths)(
+            ctx->device, acc->mode, ctx->scene.depth > 8, lds_scene, lds, acc->blocks, a, s);
         if (e != hipSuccess) return hip_fail(ctx, e, "ort_pixel_paths (accumulation pass) launch");
         acc->done = s1;
     } else if (o) {  // finished before the call: the frame again, from the stored sums
@@ -178,7 +186,7 @@ extern "C" {
 int ort_accum_begin(ort_ctx* ctx, const ort_params* params, const ort_tile* tile, ort_accum** out) {
     if (!ctx || !out) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_accum_begin: null argument");
     try {
-        return accum_begin_impl(ctx, params, tile, out);
+        return accum_begin_impl(ctx, params, tile, 0, out);
     } catch (const std::exception& ex) {
         return fail(ctx, ORT_ERR_INTERNAL, std::string("ort_accum_begin: ") + ex.what());
     }
@@ -200,7 +208,7 @@ int ort_accum_get_info(const ort_accum* accum, ort_accum_info* info) {
     if (!accum || !info) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_accum_get_info: null argument");
     info->samples_done = accum->done;
     info->samples_total = accum->p.num_samples;
-    info->device_bytes = (int64_t)(accum->state.bytes + accum->sync.bytes + accum->stage.bytes);
+    info->device_bytes = (int64_t)(accum->state.bytes + accum->sync.bytes + accum->stage.bytes + accum->mstage.bytes);
     return ORT_OK;
 }
 

@@ -115,13 +115,15 @@ void each_buffer(QueryBuffers& q, F f) {
 struct DenoiseBuffers {
     DevBuf in_color, in_hits, in_normals, out;
     DevBuf guide, col_a, col_b;
+    DevBuf in_var, var_a, var_b;  // ort_denoise_ex: the staged variance plane and the two the iterations ping-pong between
 };
 struct DenoiseState : DenoiseBuffers {
     EventPair ev;
 };
 template <class F>
 void each_buffer(DenoiseBuffers& d, F f) {
-    visit_buffers<DenoiseBuffers>(f, d.in_color, d.in_hits, d.in_normals, d.out, d.guide, d.col_a, d.col_b);
+    visit_buffers<DenoiseBuffers>(f, d.in_color, d.in_hits, d.in_normals, d.out, d.guide, d.col_a, d.col_b, d.in_var,
+                                  d.var_a, d.var_b);
 }
 
 #ifndef ORT_HEAVY_STEPS
@@ -361,18 +363,21 @@ struct ort_ctx {
 // A frame's samples accumulated over several passes (include/ort.h): the frame and tile it was
 // begun with, the samples done, and per path slot (tile-block order, as PipeArgs::total) the RNG
 // state (float2) followed by the colour sum's three planes -- 20 bytes a slot, each array read and
-// written by consecutive lanes for consecutive slots.
+// written by consecutive lanes for consecutive slots.  With ORT_ACCUM_MOMENTS a fourth float plane
+// follows them: m2, the sum of the samples' squared luminances (24 bytes a slot).
 struct ort_accum {
     ort_ctx* ctx = nullptr;
     ort_params p{};
     ort_tile t{};
     int mode = 0;          // 0 the compact layout's walk, 2 brute force
     int done = 0;
+    bool moments = false;  // ORT_ACCUM_MOMENTS: the state carries the m2 plane
     long long blocks = 0;  // 16x16 tiles
     unsigned long long scene_gen = 0;
-    DevBuf state;          // float2[slots] | float[3][slots]
+    DevBuf state;          // float2[slots] | float[3][slots] (| float[slots]: m2)
     DevBuf sync;           // the launch's cursor and done count (16 ints, zeroed before every pass)
     DevBuf stage;          // host output: the tight picture on the device (allocated by the first such pass)
+    DevBuf mstage;         // ort_accum_read_moments into host memory: the mean and the variance, tight
     EventPair ev;
 };
 
@@ -415,6 +420,7 @@ void free_accum(ort_accum* a) {
     free_buf(a->state);
     free_buf(a->sync);
     free_buf(a->stage);
+    free_buf(a->mstage);
     a->ev.destroy();
     delete a;
 }

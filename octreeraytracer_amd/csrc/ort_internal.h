@@ -109,6 +109,22 @@ int ort_debug_radiance_rays(const float* sphere_center_radius, const float* sphe
 // output->data are host pointers (d->on_device and output->is_device 0); what ort_denoise refuses
 // is refused here, with the output untouched.
 int ort_debug_denoise(const ort_denoise_desc* d, const ort_output* output);
+// TEST-ONLY: ort_denoise_ex on the host CPU, as ort_debug_denoise: the variance prefilter, the
+// iterations through denoise_pixel<true> with the variances propagated, the optional gamma.
+int ort_debug_denoise_ex(const ort_denoise_desc_ex* d, const ort_output* output);
+// TEST-ONLY: finish_pixel(v, 1) -- pow(x, 1/2.2) per channel, ORT_DENOISE_GAMMA's -- of n_pixels RGB
+// triples on the host (ort_powf is not restated in numpy; out may be rgb).
+int ort_debug_gamma(const float* rgb, int64_t n_pixels, float* out);
+// TEST-ONLY: what ort_accum_read_moments returns after samples_done (1 .. num_samples) samples of an
+// accumulation of params and tile: ort_debug_emulate_render_prefix's arguments; mean (3 floats per
+// tile pixel) and variance (1 float per tile pixel), either may be NULL.
+int ort_debug_emulate_moments(const float* sphere_center_radius, const float* sphere_mat_albedo,
+                              const float* sphere_fuzz_ri, int32_t n_spheres, const float* node_min,
+                              const float* node_max, const int32_t* children_offset,
+                              const int32_t* objects_offset, const int32_t* object_count, int32_t n_nodes,
+                              const int32_t* object_indices, int64_t n_indices, int32_t layout,
+                              const ort_params* params, const ort_tile* tile, int32_t samples_done,
+                              float* mean, float* variance);
 // ANALYSIS-ONLY: lane overlap of sampled 8x8 primary-ray blocks (tools/wave_stats.py).
 int ort_debug_wave_stats(const float* sphere_center_radius, const float* sphere_mat_albedo,
                          const float* sphere_fuzz_ri, int32_t n_spheres, const float* node_min,

@@ -1535,11 +1535,15 @@ __device__ __forceinline__ void block_account(const PipeArgs& A, int slot, int b
 // PM: 0 whole pixels, 1 SPEC samples, 2 whole pixels that record their samples' end states or
 // run the fixup list (kept apart from 0: its registers are the ones-sample frames' too), 3 a pass
 // of an accumulation (accum.inc: samples A.sample .. A.sp_chunk - 1 of every pixel, the chains'
-// states and sums kept per slot between passes; instantiated there, after every kernel of this file)
+// states and sums kept per slot between passes; instantiated there, after every kernel of this file),
+// 4 a pass that also keeps the slot's second luminance moment m2 (accum_moments.inc, after every other
+// kernel): the plane after the three colour-sum planes, read, added to and written at each sample's
+// end -- sample ends are rare next to walk steps, and nothing more lives across the walk
 template <int MODE, bool DEEP, bool LDS, int PM = 0>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_PIXEL_WAVES)))
 ort_pixel_paths(PipeArgs A) {
     constexpr bool SPEC = PM == 1;
+    constexpr bool PASS = PM == 3 || PM == 4;
     // a SPEC launch in a fall-back frame, and the fixup launch's workgroups beyond what its list
     // needs, only count themselves out (before any LDS set-up)
     const bool idle_wg = (SPEC && A.sp_ctl[2] == 0) ||
@@ -1676,7 +1680,7 @@ ort_pixel_paths(PipeArgs A) {
                                     st.x = v.x;
                                     st.y = v.y;
                                     col = ort::mk(A.fx_col[e], A.fx_col[(size_t)A.total + e], A.fx_col[2 * (size_t)A.total + e]);
-                                } else if (PM == 3) {  // the pass's first sample, from the slot's stored state and sum
+                                } else if (PASS) {  // the pass's first sample, from the slot's stored state and sum
                                     s = A.sample;
                                     if (s == 0) {
                                         ort::pixel_rng_init(A.pp, px, py, st);
@@ -1694,7 +1698,7 @@ ort_pixel_paths(PipeArgs A) {
                                 }
                                 ray = ort::primary_ray(A.pp, px, py, s, st);
                                 pixel = true;
-                            } else if (PM == 3) {  // ... of an accumulation pass: with a picture only
+                            } else if (PASS) {  // ... of an accumulation pass: with a picture only
                                 if (A.out) store_padding(reread_args(A), cy, cx);
                             } else if (!SPEC) {  // a band's padding row (past the frame): zeros, as the pipeline writes
                                 store_padding(reread_args(A), cy, cx);
@@ -1745,14 +1749,20 @@ ort_pixel_paths(PipeArgs A) {
                 }
             } else if (ended) {  // col += radiance(r) (glsl:655); the pixel's next sample, or its final colour
                 col = ort::add(col, c);
+                if (PM == 4) {  // m2 += l * l, l the sample's luminance (sample 0 starts it at 0)
+                    const float l = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+                    float* m2 = A.fx_col + 3 * (size_t)A.total + k;
+                    const float m = s == 0 ? 0.0f : *m2;
+                    *m2 = m + l * l;
+                }
                 if (PM == 2 && A.sp_cur && ((s + 1) % A.sp_chunk == 0 || s + 1 == ns))  // a chunk's end state, for SPEC
                     A.sp_cur[(size_t)(s / A.sp_chunk) * A.total + k] = make_float2(st.x, st.y);
-                if (++s < (PM == 3 ? A.sp_chunk : ns)) {
+                if (++s < (PASS ? A.sp_chunk : ns)) {
                     b = 0;
                     c = ort::mk(1.0f, 1.0f, 1.0f);
                     importance = 1.0f;
                     ray = ort::primary_ray(A.pp, px, py, s, st);
-                } else if (PM == 3) {  // the pass's last sample: the slot's state and sum, and the picture of s samples
+                } else if (PASS) {  // the pass's last sample: the slot's state and sum, and the picture of s samples
                     A.fx_st[k] = make_float2(st.x, st.y);
                     A.fx_col[k] = col.x;
                     A.fx_col[(size_t)A.total + k] = col.y;
@@ -1938,3 +1948,6 @@ __global__ void __launch_bounds__(kBlock) k_leaf16(const uint2* node, const uint
 
 // the denoiser (ort_denoise): its kernels follow every other kernel in the code object
 #include "denoise.inc"
+// Accumulations that keep luminance moments (ort_accum_begin_ex, ort_accum_read_moments): the
+// ort_pixel_paths<..., 4> instances and the moments resolve kernel, after every earlier kernel.
+#include "accum_moments.inc"

@@ -246,7 +246,7 @@ int Raytracer::renderProgressive(const Camera& cam, int samples, float* rgb, int
     int rc = ORT_OK;
     if (!accum) {
         const ort_tile t{0, width, 0, height, 0, 0};
-        if ((rc = ort_accum_begin(ctx, &p, &t, &accum)) != ORT_OK) return rc;
+        if ((rc = ort_accum_begin_ex(ctx, &p, &t, accumMoments ? ORT_ACCUM_MOMENTS : 0, &accum)) != ORT_OK) return rc;
         accumParams = p;
     } else if (std::memcmp(p.view, accumParams.view, sizeof p.view) != 0 ||
                std::memcmp(p.camera_position, accumParams.camera_position, sizeof p.camera_position) != 0 ||
@@ -261,8 +261,27 @@ int Raytracer::renderProgressive(const Camera& cam, int samples, float* rgb, int
     return rc;
 }
 
+void Raytracer::setProgressiveMoments(bool on) {
+    if (on == accumMoments) return;
+    accumMoments = on;
+    if (accum && ctx) (void)ort_accum_free(ctx, accum);  // the state has another shape: the frame starts again
+    accum = nullptr;
+}
+
+int Raytracer::readMoments(float* mean, float* variance, bool onDevice) {
+    if (group) return ORT_ERR_UNSUPPORTED;
+    if (!ctx || !accum) return ORT_ERR_INVALID_ARG;  // no renderProgressive yet
+    const ort_accum_moments m = {mean, variance, onDevice ? 1 : 0, {0, 0, 0}};
+    return ort_accum_read_moments(ctx, accum, &m, nullptr);
+}
+
 int Raytracer::denoise(const Camera& cam, const ort_tile& tile, const float* rgb, const ort_output& output,
                        const DenoiseOptions& options) {
+    return denoise(cam, tile, rgb, nullptr, 0.0f, false, output, options);
+}
+
+int Raytracer::denoise(const Camera& cam, const ort_tile& tile, const float* rgb, const float* variance, float sigmaVariance,
+                       bool gamma, const ort_output& output, const DenoiseOptions& options) {
     if (!ctx && !group && !initialize()) return ORT_ERR_HIP;
     if (group) return ORT_ERR_UNSUPPORTED;  // the denoiser runs on one context
     if (tile.width < 0 || tile.rows < 0 || tile.y0 < 0 || (tile.band_height > 0 && tile.rows > tile.band_height))
@@ -293,8 +312,9 @@ int Raytracer::denoise(const Camera& cam, const ort_tile& tile, const float* rgb
         const int rc = traceCamera(cam, tile, q);
         if (rc != ORT_OK) return rc;
     }
-    ort_denoise_desc d;
-    std::memset(&d, 0, sizeof d);
+    ort_denoise_desc_ex x;
+    std::memset(&x, 0, sizeof x);
+    ort_denoise_desc& d = x.base;
     d.color = rgb;
     d.hits = q.hits;
     d.normals = q.normals;
@@ -306,7 +326,15 @@ int Raytracer::denoise(const Camera& cam, const ort_tile& tile, const float* rgb
     d.sigma_depth = options.sigmaDepth;
     d.normal_power = options.normalPower;
     d.flags = options.sameSphere ? ORT_DENOISE_SAME_SPHERE : 0;
-    const int rc = ort_denoise(ctx, &d, &output, nullptr);
+    int rc;
+    if (!variance && !gamma && sigmaVariance == 0.0f) {
+        rc = ort_denoise(ctx, &d, &output, nullptr);
+    } else {
+        if (gamma) d.flags |= ORT_DENOISE_GAMMA;
+        x.variance = variance;
+        x.sigma_variance = sigmaVariance;
+        rc = ort_denoise_ex(ctx, &x, &output, nullptr);
+    }
     if (rc != ORT_OK || real == tile.rows || !output.data) return rc;
     // the padding rows as render writes them: zero bytes
     const size_t rowBytes = (size_t)tile.width * (output.format == ORT_FORMAT_RGBA8 ? 4 : 12);

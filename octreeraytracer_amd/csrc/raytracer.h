@@ -147,6 +147,18 @@ public:
     // group: ORT_ERR_UNSUPPORTED).
     int denoise(const Camera& cam, const ort_tile& tile, const float* rgb, const ort_output& output,
                 const DenoiseOptions& options = {});
+    // The camera at rest (include/ort.h ort_accum_begin_ex, ort_accum_read_moments, ort_denoise_ex):
+    // with setProgressiveMoments(true) renderProgressive's accumulation also keeps each pixel's
+    // second luminance moment (the switch starts the accumulation again); readMoments writes the
+    // linear mean (nullptr, or width * height * 3 floats) and the variance of its luminance (nullptr,
+    // or width * height floats; -1: no estimate) of the samples done so far, host memory or, with
+    // onDevice, device memory; and this denoise filters such a mean guided by that variance
+    // (nullptr: the term off) -- taps further than sigmaVariance standard deviations add nothing --
+    // and, with gamma, writes pow(result, 1/2.2), the display picture.  variance lives where rgb does.
+    void setProgressiveMoments(bool on);
+    int readMoments(float* mean, float* variance, bool onDevice = false);
+    int denoise(const Camera& cam, const ort_tile& tile, const float* rgb, const float* variance, float sigmaVariance,
+                bool gamma, const ort_output& output, const DenoiseOptions& options = {});
 
     Camera camera;  // the reference keeps a global Camera (src/main.cpp:18); pose set like main()
     const RaytracerConfig& config() const { return cfg; }
@@ -189,6 +201,7 @@ private:
     int renderRun();               // one frame of run(): into dframe, or into `frame` with readback
     ort_accum* accum = nullptr;    // renderProgressive's accumulation (the context owns it) and its camera
     ort_params accumParams{};
+    bool accumMoments = false;     // setProgressiveMoments
     double gpuBuildSeconds = 0.0;
     StatsWork work;               // counted after the timed frames when cfg.extendedStats
 

@@ -2041,11 +2041,14 @@ ORT_FN uint32_t pack_rgba8(V3 v) {
 // done: the samples taken, P.ns by default; fewer is the picture an accumulation shows after
 // `done` samples (ort_accum_render): the first `done` samples of the P.ns-sample chain, in P.ns's
 // strata, divided by `done`.
+// sum_out, m2_out (host emulation of ort_accum_read_moments): the linear colour sum of those
+// samples and the sum of their squared luminances, as a moments pass keeps them.
 template <int MODE, bool COUNT, class Frames>
 ORT_FN V3 shade_pixel(const PixelParams& P, const KScene& S, const float* planes, const float* planes_b,
                       const uint8_t* rank_lut, Frames& fr, int* snode, float* stmin, int px, int py, Counters& cnt,
-                      int done = -1) {
+                      int done = -1, V3* sum_out = nullptr, float* m2_out = nullptr) {
     if (done < 0) done = P.ns;
+    float m2 = 0.0f;
     ort_rng st;
     pixel_rng_init(P, px, py, st);
     V3 col = mk(0.0f, 0.0f, 0.0f);
@@ -2066,7 +2069,13 @@ ORT_FN V3 shade_pixel(const PixelParams& P, const KScene& S, const float* planes
                 break;
         }
         col = add(col, c);
+        if (m2_out) {
+            const float l = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+            m2 = m2 + l * l;
+        }
     }
+    if (sum_out) *sum_out = col;
+    if (m2_out) *m2_out = m2;
     return finish_pixel(col, done);
 }
 

@@ -335,10 +335,13 @@ class Renderer:
         return o, out
 
     # -- progressive frames -----------------------------------------------------------
-    def accumulate(self, params: FrameParams, tile: Tile | None = None) -> "Accumulation":
+    def accumulate(self, params: FrameParams, tile: Tile | None = None, moments: bool = False) -> "Accumulation":
         """Begin accumulating the frame `params` (its num_samples is the target N) over several
-        calls: ort_accum_begin (include/ort.h).  Allocates the per-pixel state, traces nothing."""
-        return Accumulation(self, params, tile or Tile.full(params))
+        calls: ort_accum_begin (include/ort.h).  Allocates the per-pixel state, traces nothing.
+        moments: the passes also keep each pixel's sum of squared sample luminances (ort_accum_begin_ex
+        with ORT_ACCUM_MOMENTS, 4 bytes more per path slot), which ``Accumulation.moments`` turns
+        into a per-pixel variance; the pictures are the same bit for bit."""
+        return Accumulation(self, params, tile or Tile.full(params), moments)
 
     # -- ray queries ------------------------------------------------------------------
     def _device_arg(self, who, x, what, dtype_name, need):
@@ -665,7 +668,8 @@ class Renderer:
     # -- denoiser ---------------------------------------------------------------------
     def denoise(self, image, guides=None, *, params: FrameParams | None = None, tile: Tile | None = None,
                 iterations: int = 3, sigma_color: float = 0.0, sigma_depth: float = 0.0, normal_power: int = 5,
-                same_sphere: bool = True, format: str = "rgb32f", row_pitch: int | None = None, out=None, stream=None):
+                same_sphere: bool = True, format: str = "rgb32f", row_pitch: int | None = None, out=None, stream=None,
+                variance=None, sigma_variance: float | None = None, gamma: bool = False):
         """Filter a few-sample picture with the guided a-trous filter (ort_denoise, include/ort.h):
         `iterations` passes of a 5x5 B3-spline kernel with step 1, 2, 4, ..., whose taps are weighted
         by the guides -- normals (normal_power squarings of the clamped dot product), depth
@@ -684,7 +688,14 @@ class Renderer:
         as taps and come out as ``render`` writes them (zeros).  Within 2 (2^iterations - 1) pixels
         of the tile's border the result differs from the whole frame's filter.
         format, row_pitch, out, stream: as ``render`` (place is "tile"); out may be the image itself
-        (in place).  Returns out."""
+        (in place).
+        variance: None, or the (rows, width) float32 variance of the image's luminance, of the image's
+        kind, as ``Accumulation.moments`` returns it beside the linear mean: adds the variance-guided
+        term of ort_denoise_ex, which only takes taps within sigma_variance (default
+        DEFAULT_SIGMA_VARIANCE) standard deviations of the pixel's luminance and so closes itself as
+        the picture converges.  gamma: the output is pow(result, 1/2.2), the render path's: filter
+        the linear mean and get the display picture.  Without all three the call is ort_denoise.
+        Returns out."""
         who = "denoise"
         device = not isinstance(image, np.ndarray)
         rows, width, pitch, color = _denoise_image(who, image, self.device if device else None)
@@ -724,7 +735,12 @@ class Renderer:
         d = _denoise_desc(color, pitch, hits, nrm, width, real, device, iterations, sigma_color, sigma_depth, normal_power,
                           same_sphere)
         s = C.c_void_p(int(stream)) if stream else None
-        self._check(self._lib.ort_denoise(self._ctx, C.byref(d), C.byref(o), s))
+        if variance is None and sigma_variance is None and not gamma:
+            self._check(self._lib.ort_denoise(self._ctx, C.byref(d), C.byref(o), s))
+        else:
+            x, keep_v = _denoise_desc_ex(who, d, variance, sigma_variance, gamma, rows, width, real, self if device else None)
+            self._check(self._lib.ort_denoise_ex(self._ctx, C.byref(x), C.byref(o), s))
+            del keep_v
         del keep
         if real < rows:  # after the call: a refused one leaves out untouched
             _denoise_zero_rows(who, out, real, rows, o.row_pitch_bytes or width * L.FORMAT_BPP[o.format],
@@ -787,13 +803,18 @@ class Accumulation:
     A context manager: leaving it frees the state (as ``close`` does; the renderer's ``close``
     frees what is left)."""
 
-    def __init__(self, renderer: Renderer, params: FrameParams, tile: Tile):
+    def __init__(self, renderer: Renderer, params: FrameParams, tile: Tile, moments: bool = False):
         self._r = renderer
         self._h = C.c_void_p()
         self.params, self.tile = params, tile
+        self.keeps_moments = bool(moments)
         self._guides = None
         p, t = params.to_c(), tile.to_c()
-        renderer._check(renderer._lib.ort_accum_begin(renderer._ctx, C.byref(p), C.byref(t), C.byref(self._h)))
+        if moments:
+            renderer._check(renderer._lib.ort_accum_begin_ex(renderer._ctx, C.byref(p), C.byref(t), L.ORT_ACCUM_MOMENTS,
+                                                             C.byref(self._h)))
+        else:
+            renderer._check(renderer._lib.ort_accum_begin(renderer._ctx, C.byref(p), C.byref(t), C.byref(self._h)))
 
     def close(self):
         if self._h and self._r._ctx:
@@ -844,6 +865,52 @@ class Accumulation:
         o, out = r._output("step", self.params, self.tile, out, format, row_pitch, place)
         r._check(r._lib.ort_accum_render(r._ctx, self._h, int(n), C.byref(o), s))
         return out
+
+    def moments(self, mean: bool = True, variance: bool = True, out_mean=None, out_variance=None, stream=None):
+        """The linear mean (rows, width, 3) of the samples done so far -- the picture before its gamma
+        -- and the variance (rows, width) of that mean's luminance, -1 where there is no estimate
+        (fewer than 2 samples, rows past the frame): ort_accum_read_moments (include/ort.h).  The
+        variance needs ``accumulate(..., moments=True)``.  Returns numpy arrays, or, given torch CUDA
+        tensors (or device pointers) as out_mean / out_variance, writes and returns those; both
+        outputs are of one kind.  Returns (mean, variance), or the one asked for."""
+        r = self._r
+        who = "moments"
+        if not mean and not variance:
+            raise ValueError(f"{who}: ask for the mean, the variance or both")
+        if (out_mean is not None and not mean) or (out_variance is not None and not variance):
+            raise ValueError(f"{who}: an out for something that was not asked for")
+        rows, width = int(self.tile.rows), int(self.tile.width)
+        n = rows * width
+        given = [o for o in (out_mean, out_variance) if o is not None]
+        device = any(not isinstance(o, np.ndarray) for o in given)
+        if device and any(isinstance(o, np.ndarray) for o in given):
+            raise ValueError(f"{who}: out_mean and out_variance must both be numpy arrays or both live on the device")
+        m = L.OrtAccumMoments()
+        m.on_device = 1 if device else 0
+        outs = []
+        for want, out, what, ch in ((mean, out_mean, "out_mean", 3), (variance, out_variance, "out_variance", 1)):
+            if not want:
+                continue
+            shape = (rows, width, 3) if ch == 3 else (rows, width)
+            if device:
+                if out is None:
+                    import torch
+                    out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", r.device))
+                ptr = r._device_arg(who, out, what, "float32", 4 * ch * n)
+            else:
+                if out is None:
+                    out = np.empty(shape, np.float32)
+                if out.dtype != np.float32 or not out.flags.c_contiguous or out.size != ch * n:
+                    raise ValueError(f"{who}: {what} must be a C-contiguous float32 array of {ch * n} elements")
+                ptr = out.ctypes.data
+            if ch == 3:
+                m.mean = C.c_void_p(ptr)
+            else:
+                m.variance = C.c_void_p(ptr)
+            outs.append(out)
+        s = C.c_void_p(int(stream)) if stream else None
+        r._check(r._lib.ort_accum_read_moments(r._ctx, self._h, C.byref(m), s))
+        return tuple(outs) if len(outs) == 2 else outs[0]
 
     def restart(self, params: FrameParams):
         """A new camera for the same shape (width, height, num_samples, max_depth, use_octree):
@@ -1139,9 +1206,39 @@ def _denoise_desc(color, pitch, hits, normals, width, rows, device, iterations, 
     return d
 
 
+# Renderer.denoise's sigma_variance when a variance is given: taps further than this many standard
+# deviations of the pixel's luminance add nothing (chosen from a sweep over 1, 2, 4 and 8: DESIGN.md 4.15).
+DEFAULT_SIGMA_VARIANCE = 4.0
+
+
+def _denoise_desc_ex(who, d, variance, sigma_variance, gamma, rows, width, real, renderer):
+    """The ort_denoise_desc_ex over the description d, and what to keep alive during the call."""
+    x = L.OrtDenoiseDescEx()
+    x.base = d
+    if gamma:
+        x.base.flags |= L.ORT_DENOISE_GAMMA
+    keep = None
+    if variance is None:
+        if sigma_variance is not None:
+            raise ValueError(f"{who}: sigma_variance needs a variance")
+        return x, keep
+    n = rows * width
+    if renderer is None:
+        if (not isinstance(variance, np.ndarray) or variance.dtype != np.float32 or not variance.flags.c_contiguous or
+                variance.size != n):
+            raise ValueError(f"{who}: variance must be a C-contiguous float32 array of {n} elements")
+        x.variance = C.c_void_p(variance.ctypes.data)
+    else:
+        if hasattr(variance, "numel") and variance.numel() != n:
+            raise ValueError(f"{who}: variance must hold {n} elements")
+        x.variance = C.c_void_p(renderer._device_arg(who, variance, "variance", "float32", 4 * n))
+    x.sigma_variance = float(DEFAULT_SIGMA_VARIANCE if sigma_variance is None else sigma_variance)
+    return x, variance
+
+
 def denoise_host(image, guides, *, iterations: int = 3, sigma_color: float = 0.0, sigma_depth: float = 0.0,
                  normal_power: int = 5, same_sphere: bool = True, format: str = "rgb32f", row_pitch: int | None = None,
-                 out=None):
+                 out=None, variance=None, sigma_variance: float | None = None, gamma: bool = False):
     """TEST-ONLY: ``Renderer.denoise`` on the host CPU (ort_debug_denoise: denoise.inc's denoise_pixel,
     the kernels' own per-pixel function).  image, guides, format, row_pitch, out: as there, numpy
     arrays; out may be the image itself.  Returns out."""
@@ -1154,6 +1251,49 @@ def denoise_host(image, guides, *, iterations: int = 3, sigma_color: float = 0.0
     o, out = Renderer._output(None, who, None, Tile(0, width, 0, rows), out, format, row_pitch, "tile")
     d = _denoise_desc(color, pitch, hits, nrm, width, rows, False, iterations, sigma_color, sigma_depth, normal_power,
                       same_sphere)
-    L.acheck(lib.ort_debug_denoise(C.byref(d), C.byref(o)))
+    if variance is None and sigma_variance is None and not gamma:
+        L.acheck(lib.ort_debug_denoise(C.byref(d), C.byref(o)))
+    else:  # ort_debug_denoise_ex: the emulation of ort_denoise_ex
+        x, keep_v = _denoise_desc_ex(who, d, variance, sigma_variance, gamma, rows, width, rows, None)
+        L.acheck(lib.ort_debug_denoise_ex(C.byref(x), C.byref(o)))
+        del keep_v
     del keep
+    return out
+
+
+def accum_moments_host(spheres: SphereSet, tree: FlatOctree | None, params: FrameParams, tile: Tile | None = None,
+                       layout: int = L.ORT_LAYOUT_COMPACT, samples_done: int | None = None):
+    """TEST-ONLY: ``Accumulation.moments`` after samples_done (default: all) samples on the host CPU
+    (ort_debug_emulate_moments: the kernel's per-pixel code with its colour sum and second moment).
+    Returns (mean (rows, width, 3), variance (rows, width))."""
+    lib = L.analysis_lib()
+    tile = tile or Tile.full(params)
+    mean = np.empty((tile.rows, tile.width, 3), np.float32)
+    var = np.empty((tile.rows, tile.width), np.float32)
+    p, t = params.to_c(), tile.to_c()
+    cr = np.ascontiguousarray(spheres.center_radius, np.float32)
+    ma = np.ascontiguousarray(spheres.mat_albedo, np.float32)
+    fr = np.ascontiguousarray(spheres.fuzz_ri, np.float32)
+    if tree is None:
+        keep = ()
+        args = (None, None, None, None, None, 0, None, 0)
+    else:
+        keep = tuple(np.ascontiguousarray(a, t_) for a, t_ in (
+            (tree.node_min, np.float32), (tree.node_max, np.float32), (tree.children_offset, np.int32),
+            (tree.objects_offset, np.int32), (tree.object_count, np.int32), (tree.object_indices, np.int32)))
+        args = (L.fptr(keep[0]), L.fptr(keep[1]), L.iptr(keep[2]), L.iptr(keep[3]), L.iptr(keep[4]),
+                tree.n_nodes, L.iptr(keep[5]), tree.n_indices)
+    k = params.num_samples if samples_done is None else int(samples_done)
+    L.acheck(lib.ort_debug_emulate_moments(L.fptr(cr), L.fptr(ma), L.fptr(fr), spheres.n, *args, layout, C.byref(p),
+                                          C.byref(t), k, L.fptr(mean), L.fptr(var)))
+    del keep
+    return mean, var
+
+
+def gamma_host(rgb):
+    """TEST-ONLY: pow(x, 1/2.2) per channel as the kernels compute it (ort_debug_gamma: finish_pixel)."""
+    lib = L.analysis_lib()
+    a = np.ascontiguousarray(rgb, np.float32)
+    out = np.empty_like(a)
+    L.acheck(lib.ort_debug_gamma(L.fptr(a), a.size // 3, L.fptr(out)))
     return out

@@ -4,7 +4,11 @@ without speculation (ort_last_kernel_ms) against the sum of ort_accum_last_pass_
 of one frame -- 16 x 1, 4 x 4 and 1 x 16 samples, without and with a float picture per pass --
 on config_default and stats114.  Median (min-max) of --reps repetitions after --warmup; every
 accumulated frame is checked against the case's canonical SHA-256.  Prints one JSON line.
-Run it on two builds alternately to compare their one-shot frames."""
+Run it on two builds alternately to compare their one-shot frames.
+--moments times instead the passes of an accumulation that keeps luminance moments
+(Renderer.accumulate(moments=True)) against the plain accumulation's, the two alternating repetition
+by repetition in one process: 1 pass of N and N passes of 1, no picture; *_ratio is the median of the
+per-repetition moments / plain ratios."""
 import argparse
 import json
 import statistics
@@ -21,6 +25,7 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=31)
     ap.add_argument("--cases", default="config_default,stats114")
+    ap.add_argument("--moments", action="store_true", help="moments passes against plain passes (see above)")
     a = ap.parse_args(argv)
     import torch
 
@@ -39,6 +44,30 @@ def main(argv=None):
             r.upload(s, t)
             r.set_pixel_paths(1)
             r.set_pixel_speculate(0)
+            if a.moments:
+                n = p.num_samples
+                for passes in (1, n):
+                    split = [n // passes] * passes
+                    tot = {False: [], True: []}
+                    with r.accumulate(p) as plain, r.accumulate(p, moments=True) as mom:
+                        for i in range(a.warmup + a.reps):
+                            for acc, key in ((plain, False), (mom, True)) if i % 2 == 0 else ((mom, True), (plain, False)):
+                                acc.restart(p)
+                                sm = 0.0
+                                for k in split:
+                                    acc.step(k, out=False)
+                                    sm += acc.last_pass_ms()
+                                if i >= a.warmup:
+                                    tot[key].append(sm)
+                        for acc in (plain, mom):
+                            acc.step(1, out=dev)
+                            torch.cuda.synchronize()
+                            assert frame_sha(dev.cpu().numpy()) == c["sha256"], (name, split)
+                    tag = f"{name}.accum_{passes}x{n // passes}"
+                    res[f"{tag}_plain_ms"] = summary(tot[False])
+                    res[f"{tag}_moments_ms"] = summary(tot[True])
+                    res[f"{tag}_ratio"] = summary([m / q for m, q in zip(tot[True], tot[False])])
+                continue
             ms = []
             for i in range(a.warmup + a.reps):
                 r.render(p, out=dev)

@@ -21,7 +21,14 @@ that picture with the accumulation's guides.
 
 Writes ab.md and ab.json into --out (default profiles/denoise); --bench-log appends the lines of a
 file (the plain bench.py runs on this change and on its parent) to the .md.
-usage: python tools/denoise_ab.py [--calls 50] [--warmup 5] [--out DIR]     (GPU)
+--variance adds, at every point and in the same rounds, ort_denoise_ex with a seeded
+variance plane (the variance-guided term on, sigma_variance at its default) right after the plain
+ort_denoise, the ratio of the two per round, and the rest loop at config.h's default frame: a
+one-sample moments pass, ort_accum_read_moments and the variance-guided denoise with gamma of its
+mean, beside the plain pass and the plain denoise of its picture.  The variance plane is 4 B a pixel
+beside the records: 4 B more read by the pack pass and 4 B written, then 4 B read and 4 B written per
+iteration but the last, which only reads.  Write it somewhere else: --out profiles/variance.
+usage: python tools/denoise_ab.py [--calls 50] [--warmup 5] [--out DIR] [--variance]     (GPU)
 """
 import argparse
 import json
@@ -53,6 +60,11 @@ def compulsory_bytes(pixels, iterations, fmt):
     return pixels * (32 + 32 + iterations * 32 + (iterations - 1) * 16 + last)
 
 
+def variance_bytes(pixels, iterations):
+    """The bytes the variance plane adds to compulsory_bytes (see the module text)."""
+    return pixels * (4 + 4 + iterations * 4 + (iterations - 1) * 4)
+
+
 def guide_field(w, h, dev):
     """{t bits, sphere} records and normals: 40 discs of their own ids and normals over misses."""
     rng = np.random.default_rng(3)
@@ -77,6 +89,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "denoise"))
     ap.add_argument("--bench-log", default="")
+    ap.add_argument("--variance", action="store_true", help="also ort_denoise_ex with a variance plane, and the rest loop")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     res = {"device": torch.cuda.get_device_name(0), "calls": a.calls, "warmup": a.warmup, "kernel": "direct", "points": []}
@@ -92,13 +105,20 @@ def main():
                     half = compulsory_bytes(w * h, n_it, fmt) // 2
                     points.append(dict(w=w, h=h, iterations=n_it, format=fmt, img=img, rec=rec, nrm=nrm, out=out, share=share,
                                        src=torch.empty(half, dtype=torch.uint8, device=dev),
-                                       dst=torch.empty(half, dtype=torch.uint8, device=dev), ms=[], copy=[]))
+                                       dst=torch.empty(half, dtype=torch.uint8, device=dev), ms=[], copy=[], vms=[],
+                                       var=torch.rand((h, w), dtype=torch.float32, device=dev,
+                                                      generator=torch.Generator(device=dev).manual_seed(2)) * 0.05))
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for i in range(a.warmup + a.calls):
             for q in points:
                 r.denoise(q["img"], (q["rec"], q["nrm"]), iterations=q["iterations"], format=q["format"], out=q["out"])
                 t_d = r.last_denoise_ms()
+                if a.variance:
+                    r.denoise(q["img"], (q["rec"], q["nrm"]), iterations=q["iterations"], format=q["format"], out=q["out"],
+                              variance=q["var"])
+                    if i >= a.warmup:
+                        q["vms"].append(r.last_denoise_ms())
                 e0.record()
                 q["dst"].copy_(q["src"])
                 e1.record()
@@ -127,6 +147,39 @@ def main():
                     den_ms.append(t_d)
             r.trace_camera(p, which="pixel_centre", normals=g[1], out=g[0])
             guides_ms = r.last_query_ms()
+    rest = None
+    if a.variance:  # the rest loop: moments pass, read, variance-guided denoise; beside the plain pass and denoise
+        with ort.Renderer(0) as r:
+            r.build_scene(s, DEPTH, 0)
+            p16 = ort.FrameParams.default_camera(W, H, num_samples=16, max_depth=BOUNCES)
+            mean = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+            var = torch.empty((H, W), dtype=torch.float32, device=dev)
+            ts = torch.cuda.Stream(device=dev)
+            t = dict(plain_pass=[], moments_pass=[], read=[], plain_denoise=[], var_denoise=[])
+            with r.accumulate(p16) as plain, r.accumulate(p16, moments=True) as mom:
+                g = mom.guides()
+                torch.cuda.synchronize()
+                for i in range(a.warmup + a.calls):
+                    row = {}
+                    for acc, key in ((plain, "plain_pass"), (mom, "moments_pass")) if i % 2 == 0 else ((mom, "moments_pass"), (plain, "plain_pass")):
+                        acc.restart(p16)
+                        acc.step(1, out=False)
+                        acc.step(1, out=pic)           # the second one-sample pass: a variance exists after it
+                        row[key] = acc.last_pass_ms()
+                    torch.cuda.synchronize()
+                    e0.record(ts)
+                    mom.moments(out_mean=mean, out_variance=var, stream=ts.cuda_stream)
+                    e1.record(ts)
+                    e1.synchronize()
+                    row["read"] = e0.elapsed_time(e1)
+                    r.denoise(pic, g, out=flt)
+                    row["plain_denoise"] = r.last_denoise_ms()
+                    r.denoise(mean, g, out=flt, variance=var, gamma=True)
+                    row["var_denoise"] = r.last_denoise_ms()
+                    if i >= a.warmup:
+                        for k, v in row.items():
+                            t[k].append(v)
+            rest = {k: dict(median=pct(v, 0.5), p10=pct(v, 0.1), p90=pct(v, 0.9)) for k, v in t.items()}
     lines = [f"ort_denoise (direct form: each lane loads its 25 taps from global memory), library defaults, device pointers, "
              f"{a.warmup} warm-up + {a.calls} timed rounds of all points in turn, one process, {res['device']}.",
              "denoise: ort_last_denoise_ms (pack pass + iterations).  copy: a device-to-device copy reading and writing the "
@@ -142,6 +195,32 @@ def main():
                                   compulsory_mb=mb, denoise_over_copy=d / c))
         lines.append(f"| {q['w']} x {q['h']} | {q['iterations']} | {q['format']} | {d:.4f} | {pct(q['ms'], 0.1):.4f}-{pct(q['ms'], 0.9):.4f} | "
                      f"{mb:.1f} | {c:.4f} | {pct(q['copy'], 0.1):.4f}-{pct(q['copy'], 0.9):.4f} | {d / c:.2f} |")
+    if a.variance:
+        lines += ["", "ort_denoise_ex with a variance plane (the variance-guided term on) right after ort_denoise, every round:", "",
+                  "| size | iterations | format | plain ms median | with variance ms median | p10-p90 | ratio median (p10-p90) | "
+                  "B / pixel / iteration plain -> with variance | with variance / copy of its bytes |", "|---|---|---|---|---|---|---|---|---|"]
+        res["variance_points"] = []
+        for q in points:
+            d, v = pct(q["ms"], 0.5), pct(q["vms"], 0.5)
+            ratios = [x / y for x, y in zip(q["vms"], q["ms"])]
+            px = q["w"] * q["h"]
+            b0 = compulsory_bytes(px, q["iterations"], q["format"])
+            b1 = b0 + variance_bytes(px, q["iterations"])
+            c = pct(q["copy"], 0.5) * b1 / b0   # the measured copy scaled to the larger byte count
+            res["variance_points"].append(dict(w=q["w"], h=q["h"], iterations=q["iterations"], format=q["format"], plain_ms=d,
+                                               variance_ms=dict(median=v, p10=pct(q["vms"], 0.1), p90=pct(q["vms"], 0.9)),
+                                               ratio=dict(median=pct(ratios, 0.5), p10=pct(ratios, 0.1), p90=pct(ratios, 0.9)),
+                                               bytes_per_pixel_iteration=[b0 / px / q["iterations"], b1 / px / q["iterations"]],
+                                               variance_over_scaled_copy=v / c))
+            lines.append(f"| {q['w']} x {q['h']} | {q['iterations']} | {q['format']} | {d:.4f} | {v:.4f} | {pct(q['vms'], 0.1):.4f}-"
+                         f"{pct(q['vms'], 0.9):.4f} | {pct(ratios, 0.5):.3f} ({pct(ratios, 0.1):.3f}-{pct(ratios, 0.9):.3f}) | "
+                         f"{b0 / px / q['iterations']:.1f} -> {b1 / px / q['iterations']:.1f} | {v / c:.2f} |")
+        res["rest_loop"] = dict(frame=[W, H], bounces=BOUNCES, **rest)
+        lines += ["", f"The rest loop at config.h's default frame ({W} x {H}, {SPHERES} spheres, {BOUNCES} bounces, 16-sample target), "
+                  "second one-sample pass, ms median (p10-p90):", ""]
+        for k, label in (("plain_pass", "plain pass"), ("moments_pass", "moments pass"), ("read", "ort_accum_read_moments (mean and variance, device)"),
+                         ("plain_denoise", "ort_denoise of the picture"), ("var_denoise", "ort_denoise_ex of the mean: variance, gamma")):
+            lines.append(f"- {label}: {rest[k]['median']:.4f} ({rest[k]['p10']:.4f}-{rest[k]['p90']:.4f})")
     res["preview"] = dict(frame=[W, H], bounces=BOUNCES, pass_ms=pct(pass_ms, 0.5), denoise_ms=pct(den_ms, 0.5), guides_ms=guides_ms)
     lines += ["", f"The preview at config.h's default frame ({W} x {H}, {SPHERES} spheres, {BOUNCES} bounces): one-sample accumulation "
               f"pass {pct(pass_ms, 0.5):.4f} ms (p10-p90 {pct(pass_ms, 0.1):.4f}-{pct(pass_ms, 0.9):.4f}), its denoise (3 iterations) "
