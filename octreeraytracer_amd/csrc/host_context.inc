@@ -189,6 +189,7 @@ struct SceneBuffers {
     DevBuf node, leaf_sph, leaf_idx, planes, kid;  // compact
     DevBuf nk;                                   // ... node records and kid entries interleaved (build_nk)
     DevBuf leaf16;                               // ... depth <= 8: the 16-byte leaf records (build_leaf16)
+    DevBuf cam_node;                             // ... depth <= 8: node[] with the repeat masks (build_cam_node)
     DevBuf lds_img;                              // compact: the workgroup LDS image (k_lds_image)
     DevBuf lds_rev;                              // ... depth 9-10: the reversed-table image (persistent kernel)
     DevBuf nodeA, nodeB, cnt, indices;           // explicit
@@ -211,7 +212,7 @@ struct Scene : SceneBuffers {
 // and ort_scene_get_info sums.
 template <class C, class F>
 void each_scene_buffer(C& c, F f) {
-    visit_buffers<SceneBuffers>(f, c.sph_cr, c.sph_ma, c.sph_fr, c.node, c.kid, c.nk, c.leaf16, c.leaf_sph, c.leaf_idx, c.planes,
+    visit_buffers<SceneBuffers>(f, c.sph_cr, c.sph_ma, c.sph_fr, c.node, c.kid, c.nk, c.leaf16, c.cam_node, c.leaf_sph, c.leaf_idx, c.planes,
                                 c.lds_img, c.lds_rev, c.nodeA, c.nodeB, c.cnt, c.indices);
 }
 

@@ -23,6 +23,7 @@ struct HostScene {
     std::vector<float> fplanes, fplanes_b;
     std::vector<uint8_t> lut;           // the rank LUT
     std::vector<uint4> leaf16;          // depth <= 8: KScene::leaf16, as k_leaf16 derives it
+    std::vector<uint2> cam_node;        // depth <= 8: KScene::cam_node, as k_cam_node derives it
     const uint8_t* rank_lut = nullptr;  // ... null for an unordered tree (and without the compact layout)
     std::string error;                  // of a failed build
     HostScene() { std::memset(&S, 0, sizeof(S)); }
@@ -73,6 +74,11 @@ struct HostScene {
                             (int64_t)(cl.leaf_sph.size() / 4), leaf16);
                 S.leaf16 = leaf16.data();
                 S.leaf16_bytes = (uint32_t)(16 * leaf16.size());
+                if (ort::Masks64::kLeafDedup) {
+                    fill_cam_node((const uint2*)cl.node.data(), leaf16, cam_node);
+                    S.cam_node = cam_node.data();
+                    S.cam_bytes = (uint32_t)(8 * cam_node.size());
+                }
             }
             fplanes.resize(ort::fast_plane_floats(cl.depth));
             ort::fill_fast_planes(cl.planes.data(), fplanes.data(), cl.depth);
@@ -108,6 +114,17 @@ struct HostScene {
             uint4 sp = make_uint4(0u, 0u, 0u, ort::kLeaf16ListTag);
             if (rec.y == 1u && (int64_t)rec.x < n_ent) sp = leaf_sph[rec.x];
             out[(size_t)i] = ort::leaf16_record(rec, sp);
+        }
+    }
+
+    // k_cam_node on the host: the same ort::leaf_repeat_masks / ort::cam_record per node
+    static void fill_cam_node(const uint2* node, const std::vector<uint4>& leaf16, std::vector<uint2>& out) {
+        const int64_t n = (int64_t)leaf16.size();
+        out.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+            const uint2 rec = node[i];
+            const uint32_t ab = ort::cam_has_masks(rec, n) ? ort::leaf_repeat_masks(&leaf16[rec.x], rec.y & 0xffu) : 0u;
+            out[(size_t)i] = ort::cam_record(rec, ab);
         }
     }
 
@@ -523,6 +540,18 @@ int64_t ort_debug_walk_steps(const float* cr, const float* ma, const float* fr, 
                              const int32_t* cnt, int32_t n_nodes, const int32_t* idx, int64_t n_indices,
                              const ort_params* p, int32_t block_step, int32_t* lens, int64_t n_lens, uint16_t* steps,
                              int64_t cap) {
+    return ort_debug_walk_steps_ex(cr, ma, fr, n_spheres, node_min, node_max, co, oo, cnt, n_nodes, idx, n_indices, p,
+                                   block_step, 0, lens, n_lens, steps, cap);
+}
+
+// production != 0 (tools/leaf_dedup_sim.py): the non-counting walk's steps -- the leaf children it
+// tested (after the repeat masks of this build's Masks64::kLeafDedup) and its sphere tests, from
+// the walk's own hooks (g_leaf_dedup, g_leaf_forms), in the same step records.
+int64_t ort_debug_walk_steps_ex(const float* cr, const float* ma, const float* fr, int32_t n_spheres,
+                                const float* node_min, const float* node_max, const int32_t* co, const int32_t* oo,
+                                const int32_t* cnt, int32_t n_nodes, const int32_t* idx, int64_t n_indices,
+                                const ort_params* p, int32_t block_step, int32_t production, int32_t* lens, int64_t n_lens,
+                                uint16_t* steps, int64_t cap) {
     try {
         if (block_step < 1) return fail(nullptr, ORT_ERR_INVALID_ARG, "bad block_step");
         HostScene hs;
@@ -547,9 +576,23 @@ int64_t ort_debug_walk_steps(const float* cr, const float* ma, const float* fr, 
                     const ort::Ray ray = ort::primary_ray(pp, px, py, 0, st);
                     const ort::V3 inv = ort::mk(1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z);
                     ort::FastStateT<ort::Masks64> fs;
-                    if (ort::fast_path_ok(ray, inv, 0.001f, ORT_MAXFLOAT) &&
+                    if (production && ort::fast_path_ok(ray, inv, 0.001f, ORT_MAXFLOAT) &&
                         ort::fast_begin(S, fplanes.data(), lut.data(), ray, inv, 0.001f, ORT_MAXFLOAT, fs)) {
                         for (bool done = false; !done;) {
+                            ort::Counters cc;
+                            const unsigned long long k0 = ort::g_leaf_dedup[0], o0 = ort::g_leaf_forms[0] + ort::g_leaf_forms[2];
+                            const uint32_t y = fs.rec.y;
+                            done = ort::fast_step<false>(S, lut.data(), fs, lf, cc);
+                            const uint64_t kids = ort::g_leaf_dedup[0] - k0;
+                            const uint64_t objs = std::min<uint64_t>(ort::g_leaf_forms[0] + ort::g_leaf_forms[2] - o0, 255);
+                            const bool lk = (y & ORT_INTERNAL_FLAG) && (y & ORT_LEAFKIDS_FLAG);
+                            if (n < cap) steps[n] = (uint16_t)(objs | (kids < 15 ? kids : 15) << 8 | (lk ? 0x8000u : 0u));
+                            ++n;
+                            ++len;
+                        }
+                    } else if (!production && ort::fast_path_ok(ray, inv, 0.001f, ORT_MAXFLOAT) &&
+                        ort::fast_begin<0>(S, fplanes.data(), lut.data(), ray, inv, 0.001f, ORT_MAXFLOAT, fs)) {
+                        for (bool done = false; !done;) {  // (the counting walk: node[] throughout)
                             ort::Counters cc;
                             for (int k = 0; k < 6; ++k) cc.v[k] = 0;
                             const uint32_t y = fs.rec.y;
@@ -657,6 +700,7 @@ int ort_debug_layout(const float* cr, int32_t n_spheres, const float* node_min, 
         else if (what == "leaf_idx") src = hs.cl.leaf_idx.data(), n = 4 * hs.cl.leaf_idx.size();
         else if (what == "planes") src = hs.cl.planes.data(), n = 4 * hs.cl.planes.size();
         else if (what == "leaf16") src = hs.leaf16.data(), n = 16 * hs.leaf16.size();
+        else if (what == "cam_node") src = hs.cam_node.data(), n = 8 * hs.cam_node.size();
         else if (what == "depth") src = &depth, n = 4;
         else if (what == "ordered") src = &ordered, n = 4;
         else return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_layout: unknown array " + what);
@@ -695,6 +739,7 @@ int ort_debug_ctx_array(ort_ctx* ctx, const char* name, void* out, int64_t cap_b
     else if (what == "planes") b = &sc.planes;
     else if (what == "nk") b = &sc.nk;
     else if (what == "leaf16") b = &sc.leaf16;
+    else if (what == "cam_node") b = &sc.cam_node;
     else if (what == "lds_img") b = &sc.lds_img;
     else if (what == "lds_rev") b = &sc.lds_rev;
     else return fail(ctx, ORT_ERR_INVALID_ARG, "ort_debug_ctx_array: unknown array " + what);
@@ -714,6 +759,17 @@ int ort_debug_leaf_forms(uint64_t* out4, int32_t reset) {
         if (out4) out4[i] = ort::g_leaf_forms[i];
         if (reset) ort::g_leaf_forms[i] = 0;
     }
+    return ORT_OK;
+}
+
+// The non-counting kLeafInline host walk's leaf children (render_core.h g_leaf_dedup): {tested,
+// dropped untested by a repeat mask}; out3[2] = Masks64::kLeafDedup of this build.
+int ort_debug_leaf_dedup(uint64_t* out3, int32_t reset) {
+    for (int i = 0; i < 2; ++i) {
+        if (out3) out3[i] = ort::g_leaf_dedup[i];
+        if (reset) ort::g_leaf_dedup[i] = 0;
+    }
+    if (out3) out3[2] = (uint64_t)ort::Masks64::kLeafDedup;
     return ORT_OK;
 }
 

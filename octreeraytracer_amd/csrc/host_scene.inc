@@ -1,5 +1,5 @@
 // Included by ort_kernel.hip after host_context.inc.  Scene upload and build: the compact layout's
-// derived arrays (LDS image, nk, leaf16), ort_upload_scene / ort_build_scene and their kin, and
+// derived arrays (LDS image, nk, leaf16, cam_node), ort_upload_scene / ort_build_scene and their kin, and
 // device_scene, the scene as the kernels take it.
 namespace {
 
@@ -37,10 +37,26 @@ int build_nk(ort_ctx* ctx) {
     return ORT_OK;
 }
 
+// The depth <= 8 camera walk pops its records from cam_node (Masks64::kLeafDedup): node[] with the
+// leaf-children nodes' repeat masks, derived from the finished leaf16 records on the same stream
+// (build_leaf16 ends with it); 8 bytes per node id.
+int build_cam_node(ort_ctx* ctx) {
+    free_buf(ctx->scene.cam_node);
+    const int64_t n = (int64_t)(ctx->scene.node.bytes / 8);
+    if (!ort::Masks64::kLeafDedup || !ctx->scene.leaf16.p || n == 0) return ORT_OK;
+    int rc;
+    if ((rc = upload(ctx, ctx->scene.cam_node, nullptr, 8 * (size_t)n))) return rc;
+    hipLaunchKernelGGL(k_cam_node, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
+                       (const uint2*)ctx->scene.node.p, (const uint4*)ctx->scene.leaf16.p, (uint2*)ctx->scene.cam_node.p, n);
+    HIPCHK(ctx, hipGetLastError());
+    return ORT_OK;
+}
+
 // The depth <= 8 camera walk reads its leaf children's records from leaf16 (Masks64::kLeafInline):
 // one per node id, 16 bytes, so at most 307 MB (a full depth-8 tree).
 int build_leaf16(ort_ctx* ctx) {
     free_buf(ctx->scene.leaf16);
+    free_buf(ctx->scene.cam_node);
     const int64_t n = (int64_t)(ctx->scene.node.bytes / 8);
     if (!ort::Masks64::kLeafInline || ctx->scene.depth > 8 || n == 0) return ORT_OK;
     int rc;
@@ -49,7 +65,7 @@ int build_leaf16(ort_ctx* ctx) {
                        (const uint2*)ctx->scene.node.p, (const uint4*)ctx->scene.leaf_sph.p, (int64_t)(ctx->scene.leaf_sph.bytes / 16),
                        (uint4*)ctx->scene.leaf16.p, n);
     HIPCHK(ctx, hipGetLastError());
-    return ORT_OK;
+    return build_cam_node(ctx);
 }
 
 // Root box for the coherence-sort key: the tree's root node, or the spheres' bounds when
@@ -228,6 +244,8 @@ ort::KScene device_scene(const ort_ctx* c) {
     S.tail_base = (uint32_t)c->scene.n_indices;
     S.leaf16 = (const uint4*)c->scene.leaf16.p;
     S.leaf16_bytes = (uint32_t)c->scene.leaf16.bytes;
+    S.cam_node = (const uint2*)c->scene.cam_node.p;
+    S.cam_bytes = (uint32_t)c->scene.cam_node.bytes;
     S.leaf_sph = (const float4*)c->scene.leaf_sph.p;
     S.node_bytes = (uint32_t)c->scene.node.bytes;
     S.leaf_bytes = (uint32_t)c->scene.leaf_sph.bytes;

@@ -176,7 +176,7 @@ int ort_debug_ctx_leaf16(ort_ctx* ctx, uint32_t* out, int64_t cap, int64_t* n);
 int ort_debug_lds_image_rev(int32_t depth, const float* planes, int32_t rev_tables, uint32_t* image, int64_t cap_words,
                             int32_t* layout);
 // TEST-ONLY: one array of the compact layout the host emulation builds for a tree, by name: "node",
-// "kid", "leaf_sph", "leaf_idx", "planes", "leaf16" (none for a tree deeper than 8), or the scalars
+// "kid", "leaf_sph", "leaf_idx", "planes", "leaf16", "cam_node" (none for a tree deeper than 8), or the scalars
 // "depth" and "ordered" (one int32 each).  *bytes = its size; copied to out when given (cap_bytes).
 int ort_debug_layout(const float* sphere_center_radius, int32_t n_spheres, const float* node_min, const float* node_max,
                      const int32_t* children_offset, const int32_t* objects_offset, const int32_t* object_count,
@@ -189,4 +189,15 @@ int ort_debug_ctx_array(ort_ctx* ctx, const char* name, void* out, int64_t cap_b
 // TEST-ONLY: sphere tests and accepted hits of the host's depth <= 8 camera walks per leaf record
 // form since the last reset: {inline tests, inline hits, list tests, list hits}.
 int ort_debug_leaf_forms(uint64_t* out4, int32_t reset);
+// TEST-ONLY: the leaf children of the non-counting host camera walks (depth <= 8) since the last
+// reset: {tested (trips of leaf_kids), dropped untested by a repeat mask (Masks64::kLeafDedup) on a
+// trip that did not hit, the build's Masks64::kLeafDedup}.
+int ort_debug_leaf_dedup(uint64_t* out3, int32_t reset);
+// ANALYSIS-ONLY: ort_debug_walk_steps with production != 0: the non-counting walk's step records
+// (leaf children tested after the build's repeat masks, sphere tests) instead of the counting walk's.
+int64_t ort_debug_walk_steps_ex(const float* sphere_center_radius, const float* sphere_mat_albedo, const float* sphere_fuzz_ri,
+                                int32_t n_spheres, const float* node_min, const float* node_max, const int32_t* children_offset,
+                                const int32_t* objects_offset, const int32_t* object_count, int32_t n_nodes,
+                                const int32_t* object_indices, int64_t n_indices, const ort_params* p, int32_t block_step,
+                                int32_t production, int32_t* lens, int64_t n_lens, uint16_t* steps, int64_t cap);
 }

@@ -1915,6 +1915,9 @@ __global__ void __launch_bounds__(kBlock) k_leaf16(const uint2* node, const uint
     leaf16[i] = ort::leaf16_record(rec, sp);
 }
 
+// KScene::cam_node (defined after every other kernel, at the end of this file, so that each keeps its place)
+__global__ void __launch_bounds__(kBlock) k_cam_node(const uint2* node, const uint4* leaf16, uint2* cam, int64_t n);
+
 }  // namespace
 
 // The host half, in the one translation unit (a kernel template is emitted where it is first
@@ -1951,3 +1954,23 @@ __global__ void __launch_bounds__(kBlock) k_leaf16(const uint2* node, const uint
 // Accumulations that keep luminance moments (ort_accum_begin_ex, ort_accum_read_moments): the
 // ort_pixel_paths<..., 4> instances and the moments resolve kernel, after every earlier kernel.
 #include "accum_moments.inc"
+
+// the camera walk's records with repeat masks (build_cam_node): last, so that every earlier kernel keeps its place
+namespace {
+// KScene::cam_node from node[] and the finished leaf16[], record by record through
+// ort::leaf_repeat_masks / ort::cam_record -- the functions the host emulation fills its own array
+// with.  A leaf-children node reads its eight children's records only where all eight lie inside the
+// arrays (cam_has_masks: co + 8 <= n).
+__global__ void __launch_bounds__(kBlock) k_cam_node(const uint2* node, const uint4* leaf16, uint2* cam, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint2 rec = node[i];
+    uint32_t ab = 0;
+    if (ort::cam_has_masks(rec, n)) {
+        uint4 k[8];
+        for (int o = 0; o < 8; ++o) k[o] = leaf16[(int64_t)rec.x + o];
+        ab = ort::leaf_repeat_masks(k, rec.y & 0xffu);
+    }
+    cam[i] = ort::cam_record(rec, ab);
+}
+}  // namespace

@@ -110,6 +110,8 @@ struct KScene {
     uint32_t tail_base;      // = n_indices: a one-sphere leaf's objectsOffset is tail_base + sphere
     const uint4* leaf16;     // depth <= 8: per node id the 16-byte leaf record (leaf16_record), or null
     uint32_t leaf16_bytes;
+    uint32_t cam_bytes;
+    const uint2* cam_node;   // depth <= 8: node[] with the leaf-children nodes' repeat masks (cam_record), or null
     // walks with Masks::kLdsScene (ort_pixel_paths on small scenes): LDS byte addresses of
     // workgroup copies of nk[] and leaf_sph[] (set inside the kernel)
     uint32_t lds_nk, lds_sph;
@@ -757,6 +759,64 @@ ORT_FN uint4 fetch_leaf16(const KScene& S, int i) {
 #endif
 }
 
+// The repeat masks of a leaf-children node (Masks64::kLeafDedup, leaf_kids): very often two or
+// three sibling one-sphere leaves carry the very same sphere, and a ray that has rejected it in one
+// of them need not test it in the others (the proof stands at leaf_kids).  k: the leaf16 records of
+// the node's eight children; cm: its child mask.  Returns A | B << 8, octant masks: A the largest
+// set of at least two existing children whose records are inline-form and equal in all four words,
+// B the next largest; equal sizes go to the set holding the lowest octant; 0 where there is none.
+ORT_FN uint32_t leaf_repeat_masks(const uint4* k, uint32_t cm) {
+    uint32_t A = 0, B = 0, seen = 0;
+    int nA = 0, nB = 0;
+    for (int o = 0; o < 8; ++o) {
+        if (!((cm >> o) & 1u) || ((seen >> o) & 1u) || (k[o].w >> 31)) continue;
+        uint32_t g = 1u << o;
+        int n = 1;
+        for (int p = o + 1; p < 8; ++p) {
+            const bool same = k[p].x == k[o].x && k[p].y == k[o].y && k[p].z == k[o].z && k[p].w == k[o].w;
+            if (((cm >> p) & 1u) && same) {
+                g |= 1u << p;
+                n += 1;
+            }
+        }
+        seen |= g;
+        if (n < 2) continue;
+        if (n > nA) {  // (sets come in the order of their lowest octant: a later one wins only if larger)
+            B = A;
+            nB = nA;
+            A = g;
+            nA = n;
+        } else if (n > nB) {
+            B = g;
+            nB = n;
+        }
+    }
+    return A | (B << 8);
+}
+// The camera walk's record of node i (KScene::cam_node): node[i], except that a leaf-children
+// node whose eight children all lie inside the tree (co + 8 <= n_nodes) carries its repeat masks:
+// A in bits 8-15 of .y -- which in node[] repeat the child mask (every existing child is a leaf) and
+// which the inline-leaves walk never reads -- and B in bits 16-23; a leaf-children node whose
+// children run past the tree carries none (both 0).  ab: leaf_repeat_masks of the node.
+constexpr uint32_t kCamMaskBits = 0x00ffff00u;
+ORT_FN bool cam_has_masks(uint2 rec, int64_t n_nodes) {
+    return (rec.y & ORT_INTERNAL_FLAG) && (rec.y & ORT_LEAFKIDS_FLAG) && (int64_t)rec.x + 8 <= n_nodes;
+}
+ORT_FN uint2 cam_record(uint2 rec, uint32_t ab) {
+    const bool lk = (rec.y & ORT_INTERNAL_FLAG) && (rec.y & ORT_LEAFKIDS_FLAG);
+    return lk ? make_uint2(rec.x, (rec.y & ~kCamMaskBits) | (ab << 8)) : rec;
+}
+ORT_FN uint2 fetch_cam(const KScene& S, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // the array's true size in the descriptor: an index outside it reads zeros, not memory
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)S.cam_node, 0, (int)S.cam_bytes, 0x00020000);
+    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, (uint32_t)i * 8u, 0, 0);
+    return make_uint2(v[0], v[1]);
+#else
+    return S.cam_node[i];
+#endif
+}
+
 // The rejected-sphere skip's kid entry of a popped node loaded in the pop beside its record
 // (its latency hidden behind the pop's plane reads) instead of in the node's step.
 #ifndef ORT_KID_PREFETCH
@@ -814,6 +874,19 @@ struct Masks64 {  // levels 0..7: trees of depth <= 8
 #endif
     static constexpr bool kLeafInline = ORT_LEAF_INLINE;
     static_assert(!kLeafInline || (kInlineLeaves && !kKidSkip), "leaf16 records: the inline leaf children, no skip");
+    // a sphere shared by sibling leaves tested once per node: the pop's record comes from
+    // KScene::cam_node, whose leaf-children nodes carry repeat masks (leaf_repeat_masks), and once
+    // a member of a mask has had its trip of leaf_kids the mask's other members are dropped.
+    // 0: the record from node[], every surviving child tested; 1: mask A only; 2: A and B.
+    // C3 in interleaved A/B: 1.4826 ms (0), 1.4213 ms (1), 1.4339 ms (2) -- B drops a few more
+    // children (the host model: 39.1 against 42.7 leaf-loop trips per block) but costs every trip
+    // three more instructions and every leaf-children node a second LUT read
+    // (profiles/leaf_dedup/ab.md): 1 ships.
+#ifndef ORT_LEAF_DEDUP
+#define ORT_LEAF_DEDUP 1
+#endif
+    static constexpr int kLeafDedup = ORT_LEAF_DEDUP;
+    static_assert(kLeafDedup >= 0 && kLeafDedup <= 2 && (!kLeafDedup || kLeafInline), "repeat masks: the leaf16 records");
     uint64_t m;
     ORT_FN void clear() { m = 0; }
     ORT_FN bool empty() const { return m == 0; }
@@ -849,6 +922,7 @@ struct Masks96 {  // levels 0..9 (ORT_COMPACT_MAX_DEPTH 10)
 #endif
     static constexpr bool kInlineLeaves = ORT_INLINE_LEAVES_DEEP;
     static constexpr bool kLeafInline = false;  // (KScene::leaf16 is built for depth <= 8 only)
+    static constexpr int kLeafDedup = 0;        // (... and KScene::cam_node)
 #ifndef ORT_PRE_MID_DEEP
 #define ORT_PRE_MID_DEEP 0
 #endif
@@ -1021,6 +1095,7 @@ struct Masks96Lean : Masks96 {
 struct Masks64Plain : Masks64 {
     static constexpr bool kInlineLeaves = false;
     static constexpr bool kLeafInline = false;
+    static constexpr int kLeafDedup = 0;
     static constexpr bool kPopTable = false;  // pops level-D leaves, which the table does not hold
     static constexpr bool kPreMid = false;
     static constexpr bool kKidSkip = true;
@@ -1053,8 +1128,14 @@ struct Masks96Split : Masks96 {
 #if defined(__HIP_DEVICE_COMPILE__)
 ORT_FN uint4 lds_u4(uint32_t a) { return *(const __attribute__((address_space(3))) uint4*)(size_t)a; }
 #endif
-template <class Masks>
+// CAM (Masks::kLeafDedup, the non-counting walk): the record from S.cam_node, with the repeat masks.
+template <bool CAM = false, class Masks>
 ORT_FN void fetch_rec(const KScene& S, int i, bool kid, FastStateT<Masks>& st) {
+    if constexpr (CAM) {
+        static_assert(!Masks::kKidSkip && !Masks::kLdsScene, "cam_node: the depth <= 8 camera walk, no kid entries");
+        st.rec = fetch_cam(S, i);
+        return;
+    }
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (Masks::kLdsScene) {  // the workgroup's copy of nk[] (ort_pixel_paths)
         const uint4 v = lds_u4(S.lds_nk + 16u * (uint32_t)i);
@@ -1074,7 +1155,9 @@ ORT_FN void fetch_rec(const KScene& S, int i, bool kid, FastStateT<Masks>& st) {
 }
 
 // Root test and state setup (glsl:296-311).  Returns false when the root box is missed.
-template <class Masks>
+// CAM: the root's record from KScene::cam_node (fetch_rec) -- by default where the walk has repeat
+// masks (Masks::kLeafDedup); 0 for a counting walk, which reads node[] throughout.
+template <int CAM = -1, class Masks>
 ORT_FN bool fast_begin(const KScene& S, const float* planes, const uint8_t* rank_lut, const Ray& r, V3 inv, float t_min,
                        float t_max, FastStateT<Masks>& st) {
     const int D = S.depth;
@@ -1143,7 +1226,7 @@ ORT_FN bool fast_begin(const KScene& S, const float* planes, const uint8_t* rank
         }
     }
     st.node = 0;
-    fetch_rec(S, 0, kKidPrefetch && Masks::kKidSkip && S.kid, st);
+    fetch_rec<(CAM < 0 ? Masks::kLeafDedup != 0 : CAM != 0)>(S, 0, kKidPrefetch && Masks::kKidSkip && S.kid, st);
     st.depth = 0;
     st.closest = t_max;
     st.hitEntry = -1;
@@ -1158,6 +1241,9 @@ ORT_FN bool fast_begin(const KScene& S, const float* planes, const uint8_t* rank
 // the kLeafInline walk per record form: {inline tests, inline hits, list tests, list hits}
 // (g_leaf_list_call: leaf_tests is running a list-form record of leaf16_tests)
 inline unsigned long long g_leaf_forms[4];
+// (ort_debug_leaf_dedup) leaf children of the non-counting kLeafInline walk: {tested (trips of
+// leaf_kids), dropped untested by a repeat mask (Masks::kLeafDedup) on a trip that did not hit}
+inline unsigned long long g_leaf_dedup[2];
 inline bool g_leaf_list_call = false;
 #endif
 
@@ -1285,13 +1371,60 @@ ORT_FN bool leaf16_tests(const KScene& S, FastStateT<Masks>& st, int kid, uint4 
 // walk after its leaf (glsl:336): no later sibling is tested.  Returns whether one hit.
 // Masks::kLeafInline (not the counting kernels, which keep the reference's loads): the child's
 // record comes from S.leaf16 instead of S.node (leaf16_tests).
+//
+// Masks::kLeafDedup: rep = the node's repeat masks as rank bits, A | B << 8 (leaf_repeat_masks
+// through the rank LUT; B only with kLeafDedup 2).  The trip of a member of A drops A's other
+// members from todo, likewise B: they hold the same sphere, bit for bit, and need no test.
+// Why that changes nothing.  Take two surviving children r < r' in rank order.  They differ on some
+// axis where r is the near half and r' the far half, so exit_r <= tM <= entry_r' on that axis'
+// mid-plane value tM, and entry_r <= exit_r because r survived child_drops: the ntmin of the trips
+// below never decreases along the loop -- for the very floats compared here, t_min and closest
+// folded into the C axis as child_drops has them.  closest does not change until a hit, and a hit
+// ends the loop.  So a sphere rejected over (ntmin, closest) -- disc <= 0 or NaN, or no root inside
+// the interval -- is rejected over every later (ntmin' >= ntmin, closest): dropping the later
+// siblings whose inline record is the same four words changes no hit, no hitEntry and no t.  If
+// the member tested hit instead, the loop is over and what is dropped does not matter.
 template <bool COUNT, class Masks>
 ORT_FN bool leaf_kids(const KScene& S, FastStateT<Masks>& st, int co, uint32_t keep, float tNA, float tMA, float tNB,
-                      float tMB, float nN, float nF, Counters& cnt) {
+                      float tMB, float nN, float nF, uint32_t rep, Counters& cnt) {
     uint32_t todo = keep;
     while (todo) {
         const int hb = 31 - __builtin_clz(todo);
         todo ^= 1u << hb;
+#if ORT_ANALYSIS && !defined(__HIP_DEVICE_COMPILE__)
+        int dropped = 0;  // (ort_debug_leaf_dedup: counted below unless this trip hits)
+#endif
+        if constexpr (!COUNT && Masks::kLeafDedup != 0) {
+            // (before the trip: its record's load covers these; a hit clears todo below anyway)
+#if defined(__HIP_DEVICE_COMPILE__)
+            // bitwise selects, as for the entries below: no v_cmp + v_cndmask.  rep's bits 8-15
+            // pass through the A mask into bits of todo that are never set
+            uint32_t a;
+            if constexpr (Masks::kLeafDedup == 1) {
+                asm("v_bfe_i32 %[a], %[rep], %[hb], 1\n\tv_and_b32 %[a], %[a], %[rep]\n\t"
+                    "v_bfi_b32 %[t], %[a], 0, %[t]"
+                    : [a] "=&v"(a), [t] "+v"(todo)
+                    : [rep] "v"(rep), [hb] "v"(hb));
+            } else {
+                uint32_t b, x;
+                asm("v_bfe_i32 %[a], %[rep], %[hb], 1\n\tv_and_b32 %[a], %[a], %[rep]\n\t"
+                    "v_lshrrev_b32 %[b], 8, %[rep]\n\tv_bfe_i32 %[x], %[b], %[hb], 1\n\t"
+                    "v_and_or_b32 %[a], %[x], %[b], %[a]\n\tv_bfi_b32 %[t], %[a], 0, %[t]"
+                    : [a] "=&v"(a), [b] "=&v"(b), [x] "=&v"(x), [t] "+v"(todo)
+                    : [rep] "v"(rep), [hb] "v"(hb));
+            }
+#else
+            const uint32_t rA = rep & 0xffu, rB = Masks::kLeafDedup == 2 ? rep >> 8 : 0u;
+            const uint32_t cut = (((rA >> hb) & 1u) ? rA : 0u) | (((rB >> hb) & 1u) ? rB : 0u);
+#if ORT_ANALYSIS
+            dropped = __builtin_popcount(todo & cut);
+#endif
+            todo &= ~cut;
+#endif
+        }
+#if ORT_ANALYSIS && !defined(__HIP_DEVICE_COMPILE__)
+        if (!COUNT && Masks::kLeafInline) g_leaf_dedup[0] += 1;
+#endif
         const uint32_t R = 7u - (uint32_t)hb;
         const int kid = co + (int)((st.otab >> (4 * R)) & 15u);
         constexpr bool kRec16 = !COUNT && Masks::kLeafInline;
@@ -1323,6 +1456,9 @@ ORT_FN bool leaf_kids(const KScene& S, FastStateT<Masks>& st, int co, uint32_t k
         bool h;
         if constexpr (kRec16) h = leaf16_tests(S, st, kid, lr, ntmin, cnt);
         else h = leaf_tests<COUNT>(S, st, (int)lr.x, (int)lr.y, ntmin, cnt);
+#if ORT_ANALYSIS && !defined(__HIP_DEVICE_COMPILE__)
+        g_leaf_dedup[1] += h ? 0ull : (unsigned long long)dropped;
+#endif
         todo = h ? 0u : todo;
     }
     return st.hit();
@@ -1395,7 +1531,13 @@ ORT_FN bool fast_visit(const KScene& S, const uint8_t* rank_lut, FastStateT<Mask
         if (Masks::kInlineLeaves && (rec.y & ORT_LEAFKIDS_FLAG)) {
             // Every existing child is a leaf, so the reference pops the surviving ones next,
             // consecutively in rank order (a leaf pushes nothing): test them right here.
-            if (leaf_kids<COUNT>(S, st, co, keep, tNA, tMA, tNB, tMB, nN, nF, cnt)) return true;
+            uint32_t rep = 0;
+            if constexpr (!COUNT && Masks::kLeafDedup != 0) {
+                // the repeat masks (st.rec came from cam_node: fetch_rec) as rank bits, LUT row m
+                rep = rank_lut[((st.otab & 7u) << 8) | ((rec.y >> 8) & 0xffu)];
+                if (Masks::kLeafDedup == 2) rep |= (uint32_t)rank_lut[((st.otab & 7u) << 8) | ((rec.y >> 16) & 0xffu)] << 8;
+            }
+            if (leaf_kids<COUNT>(S, st, co, keep, tNA, tMA, tNB, tMB, nN, nF, rep, cnt)) return true;
         } else if (Masks::kLeadLeaves) {
             // The surviving leaf children ranked before every surviving internal child are the
             // nodes the reference pops next, consecutively (a leaf pushes nothing): test them
@@ -1405,7 +1547,7 @@ ORT_FN bool fast_visit(const KScene& S, const uint8_t* rank_lut, FastStateT<Mask
             const uint32_t lead = ki ? kl & ~((2u << (31 - __builtin_clz(ki))) - 1u) : kl;
             st.masks.put(st.depth, keep ^ lead);
             fr.setCo(st.depth, co);
-            if (lead && leaf_kids<COUNT>(S, st, co, lead, tNA, tMA, tNB, tMB, nN, nF, cnt)) return true;
+            if (lead && leaf_kids<COUNT>(S, st, co, lead, tNA, tMA, tNB, tMB, nN, nF, 0u, cnt)) return true;
         } else {
             // level depth holds nothing yet (every deeper level is empty), so both writes are
             // harmless when no child survives
@@ -1465,7 +1607,7 @@ ORT_FN void fast_pop(const KScene& S, FastStateT<Masks>& st, Frames& fr) {
     const int w = 1 << (D - 1 - L);  // child width in plane steps
     st.depth = L + 1;
     st.node = fr.getCo(L) + (int)((st.otab >> (4 * rk)) & 15u);
-    fetch_rec(S, st.node, kKidPrefetch && !COUNT && Masks::kKidSkip && S.kid, st);
+    fetch_rec<(!COUNT && Masks::kLeafDedup != 0)>(S, st.node, kKidPrefetch && !COUNT && Masks::kKidSkip && S.kid, st);
 #if ORT_ANALYSIS && !defined(__HIP_DEVICE_COMPILE__)
     if (Masks::kInlineLeaves && Masks::kRevPlanes) {  // ort_debug_pop_coverage: the camera walk's pops
         g_pop_cover[hb & 63] += 1;
@@ -1545,7 +1687,7 @@ ORT_FN bool traverse_fast_t(const KScene& S, const float* planes, const uint8_t*
                             float t_min, float t_max, int& hitEntry, float& hitT, Frames& fr, Counters& cnt,
                             Ray* walked = nullptr, int* steps = nullptr) {
     FastStateT<Masks> st;
-    const bool in = fast_begin(S, planes, rank_lut, r, inv, t_min, t_max, st);
+    const bool in = fast_begin<(!COUNT && Masks::kLeafDedup != 0)>(S, planes, rank_lut, r, inv, t_min, t_max, st);
     int n = 0;  // walk steps (steps: the cost order's record; folds away without it)
     // (a leaf hold as in the deep bounce walk, lanes at a leaf waiting for company, cost the deep
     // camera walk 10-14 % at 8-16 lanes: the coherent camera rays reach leaves together anyway)
@@ -1561,7 +1703,9 @@ ORT_FN bool traverse_fast_t(const KScene& S, const float* planes, const uint8_t*
     if constexpr (!COUNT && Masks::kLeafInline) {
         // a hit in an inline-form leaf left the leaf's node id (leaf16_tests): its entry -- what
         // shading reads leaf_idx[] by -- is its record's offset, one load per hit ray
-        if (hitEntry >= kLeafIdFlag) hitEntry = (int)fetch_node(S, hitEntry ^ kLeafIdFlag).x;
+        // (a leaf's record is the same in cam_node: the walk with repeat masks reads that array alone)
+        if (hitEntry >= kLeafIdFlag)
+            hitEntry = (int)(Masks::kLeafDedup ? fetch_cam(S, hitEntry ^ kLeafIdFlag) : fetch_node(S, hitEntry ^ kLeafIdFlag)).x;
     }
     hitT = st.closest;
     return st.hit();
