@@ -82,9 +82,8 @@ struct HostScene {
             }
             fplanes.resize(ort::fast_plane_floats(cl.depth));
             ort::fill_fast_planes(cl.planes.data(), fplanes.data(), cl.depth);
-            const bool rev_b = ort::Masks96Lean::kRevPlanes || ort::fast_rev_planes(cl.depth);
-            fplanes_b.resize(ort::fast_plane_floats(cl.depth, rev_b));
-            ort::fill_fast_planes(cl.planes.data(), fplanes_b.data(), cl.depth, rev_b);
+            fplanes_b.resize(ort::fast_plane_floats(cl.depth, true));  // the bounce walks': reversed at every depth
+            ort::fill_fast_planes(cl.planes.data(), fplanes_b.data(), cl.depth, true);
             if (cl.ordered) rank_lut = lut.data();
             return ORT_OK;
         }

@@ -225,15 +225,6 @@ int split_setup(ort_ctx* ctx, const FrameFlags& F, FrameRun& R) {
     return ORT_OK;
 }
 
-#ifndef ORT_HEAVY_FIRST_STATIC_ONLY
-#define ORT_HEAVY_FIRST_STATIC_ONLY 1
-#endif
-#ifndef ORT_GEO_ALWAYS
-#define ORT_GEO_ALWAYS 0  // analysis: the rays' own classes on every frame (tools/ab_stream.py)
-#endif
-#ifndef ORT_GEO_HEAVY
-#define ORT_GEO_HEAVY 1
-#endif
 #ifndef ORT_GEO_T
 #define ORT_GEO_T 1.2f, 2.7f, 6.8f  // the class thresholds, in units of the box's smallest extent
 #endif
@@ -256,8 +247,8 @@ int heavy_first_setup(ort_ctx* ctx, const FrameFlags& F, FrameRun& R) {
         R.bcost = (uint16_t*)co.bcost.p;
         a.heavy = ctx->opt.heavy_first;
     }
-    R.bcost_rd = ((ORT_HEAVY_FIRST_STATIC_ONLY && R.cam_moved) || ORT_GEO_ALWAYS) ? nullptr : R.bcost;
-    if (ORT_GEO_HEAVY && R.bcost && !R.bcost_rd) {  // moved: classes from the rays themselves (geo_class_bits)
+    R.bcost_rd = R.cam_moved ? nullptr : R.bcost;
+    if (R.bcost && !R.bcost_rd) {  // moved: classes from the rays themselves (geo_class_bits)
         a.geo_heavy = 1;
         float m = 3.0e38f;
         for (int q = 0; q < 3; ++q) {

@@ -176,8 +176,8 @@ int pixel_lists_setup(ort_ctx* ctx, const ort_params* p, PipeArgs& a, const Pixe
     const bool spec_frame = f.kind == SpecFrame::Speculating;
     const bool heavy_first = !spec_frame &&
                              (ctx->opt.pixel_heavy_first > 0 || (ctx->opt.pixel_heavy_first < 0 && p->num_samples > 1));
-    if (ORT_PIXEL_LPT && !heavy_first && !spec_frame) pp.sig = 0;
-    if (!(ORT_PIXEL_LPT && heavy_first)) return ORT_OK;
+    if (!heavy_first && !spec_frame) pp.sig = 0;
+    if (!heavy_first) return ORT_OK;
     // last frame's class lists (same shape) and this frame's
     const size_t nb = (size_t)f.blocks * (kBlock / 64), cnt_b = 2 * kPixelClasses * sizeof(int);
     int rc;
@@ -239,7 +239,7 @@ int launch_spec_frame(ort_ctx* ctx, const ort_tile* t, int mode, PipeArgs& a, co
     a.fx_col = (float*)(fx + 4 * slots);
     PipeArgs as = a;  // the samples: no fixup list; heavy blocks first by the lists the last
     as.fx_slot = nullptr;  // whole-chain frame of this shape wrote (read only: SPEC frames keep them)
-    if (ORT_PIXEL_LPT && ctx->pp.sig == f.sig && ctx->pp.list.p) {
+    if (ctx->pp.sig == f.sig && ctx->pp.list.p) {
         const size_t nbk = (size_t)f.blocks * (kBlock / 64);
         const int r = ctx->pp.par ^ 1;
         as.pl_stride = (int)nbk;

@@ -27,7 +27,7 @@ int build_lds_image(ort_ctx* ctx) {
 int build_nk(ort_ctx* ctx) {
     free_buf(ctx->scene.nk);
     const int64_t n = (int64_t)(ctx->scene.node.bytes / 8);
-    if (!ORT_NODE_KID || !ctx->scene.kid.p || ctx->scene.kid.bytes < ctx->scene.node.bytes || n == 0 || 16 * n >= (int64_t)UINT32_MAX)
+    if (!ctx->scene.kid.p || ctx->scene.kid.bytes < ctx->scene.node.bytes || n == 0 || 16 * n >= (int64_t)UINT32_MAX)
         return ORT_OK;
     int rc;
     if ((rc = upload(ctx, ctx->scene.nk, nullptr, 16 * (size_t)n))) return rc;

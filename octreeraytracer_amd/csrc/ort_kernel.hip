@@ -173,14 +173,14 @@ __host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t
 
 constexpr size_t kRankLutBytes = 8 * 256;  // ort::rank_lut_entry table
 
-// The persistent bounce kernel at depth 9-10 (Masks96Lean with ORT_REV_BOUNCE): 512-thread
+// The persistent bounce kernel at depth 9-10 (Masks96Lean): 512-thread
 // workgroups over the reversed-table image (fast_rev_planes: 32.8 KB at depth 10, the rank
 // LUT in its gap), 53.3 KB of LDS with 512 lanes' frames -- 3 workgroups = 6 waves/SIMD.
-constexpr bool kRevBounce = ORT_REV_BOUNCE;
+constexpr bool kRevBounce = ort::Masks96Lean::kRevPlanes;  // (true)
 #ifndef ORT_PERSIST_DEEP_BLOCK
 #define ORT_PERSIST_DEEP_BLOCK 512
 #endif
-constexpr int kPersistDeepBlock = kRevBounce ? ORT_PERSIST_DEEP_BLOCK : kBlock;
+constexpr int kPersistDeepBlock = ORT_PERSIST_DEEP_BLOCK;
 
 // with_tm: the exact walk also keeps a per-level tmin column; the fast walk needs none.
 // rev / nb: the image layout and workgroup size (the deep persistent kernel's: true, 512).
@@ -257,11 +257,7 @@ __device__ inline LdsView setup_lds(unsigned char* smem, const ort::KScene& S) {
 // run covers about a fifteenth of a tile row.  Measured (interleaved A/B): 8-tile runs are
 // best at 1920 px (120 tiles per row; 16 is 1.9 % slower), 16-tile runs at 3840 px (+1.2 %
 // over 8).
-#ifndef ORT_XRUN_LOG2
-#define ORT_XRUN_LOG2 -1  // A/B builds: a fixed run length (log2); -1: from the frame width
-#endif
 inline int xcd_run_log2(int tilesX) {
-    if (ORT_XRUN_LOG2 >= 0) return ORT_XRUN_LOG2;
     int lr = 0;
     while (lr < 6 && (2 << lr) * 15 <= tilesX) ++lr;
     return lr;
@@ -1491,9 +1487,7 @@ __device__ __forceinline__ bool pixel_trace(const PipeArgs& A, const ort::KScene
     return ort::traverse_compact<false>(S, L.planes, r, 0.001f, ORT_MAXFLOAT, entry, t, L.fr, cnt);
 }
 
-#ifndef ORT_PIXEL_LPT
-#define ORT_PIXEL_LPT 1  // whole-pixel paths take last frame's heaviest 8x8 blocks first
-#endif
+// Whole-pixel paths take last frame's heaviest 8x8 blocks first (ORT_OPT_PIXEL_HEAVY_FIRST).
 constexpr int kPixelClasses = 32;  // cost classes of a block: mean bounces per sample in quarters
 // Accounts one slot of a block (a finished pixel and the bounces it traced, or a slot that is no
 // pixel): the block's last slot files the block under its cost class for the next frame and
@@ -1584,14 +1578,14 @@ ort_pixel_paths(PipeArgs A) {
     const int n_blocks = A.total >> 6;
     const int n_items = SPEC ? n_blocks * A.sp_nch : (fixup ? (*A.fx_n + 63) >> 6 : n_blocks);
     int cls_end = 0;
-    if (ORT_PIXEL_LPT && A.pl_r) {
+    if (A.pl_r) {
         cls_end = lane < kPixelClasses ? A.pl_rcnt[lane] : 0;
         for (int d = 1; d < kPixelClasses; d <<= 1) {
             const int v = __shfl_up(cls_end, d);
             if (lane >= d) cls_end += v;
         }
     }
-    const bool listed = ORT_PIXEL_LPT && !fixup && A.pl_r && __shfl(cls_end, kPixelClasses - 1) == n_blocks;
+    const bool listed = !fixup && A.pl_r && __shfl(cls_end, kPixelClasses - 1) == n_blocks;
     int k = -1;              // the lane's path slot (pixel), -1 idle
     int nb = 0;              // bounces traced for the lane's pixel so far (its cost class)
     int px = 0, py = 0, s = 0, b = 0;
@@ -1704,7 +1698,7 @@ ort_pixel_paths(PipeArgs A) {
                                 store_padding(reread_args(A), cy, cx);
                             }
                         }
-                        if (ORT_PIXEL_LPT && !SPEC && A.pl_w && !pixel) block_account(A, cand, 0);
+                        if (!SPEC && A.pl_w && !pixel) block_account(A, cand, 0);
                     }
                 }
                 next += take;
@@ -1778,7 +1772,7 @@ ort_pixel_paths(PipeArgs A) {
                     int cx, cy;
                     (void)slot_coords(A, k, cx, cy);
                     store_pixel(reread_args(A), cy, cx, py, ort::finish_pixel(col, ns));
-                    if (ORT_PIXEL_LPT && A.pl_w) block_account(A, k, nb);  // its block's cost for the next frame
+                    if (A.pl_w) block_account(A, k, nb);  // its block's cost for the next frame
                     k = -1;
                 }
             }
@@ -1808,7 +1802,7 @@ ort_pixel_paths(PipeArgs A) {
                 atomicExch(A.fx_n, 0);
             }
             // the class counts read this frame become the next frame's write counts
-            if (ORT_PIXEL_LPT && A.pl_rcnt && !SPEC)  // (SPEC frames read the lists, and keep them)
+            if (A.pl_rcnt && !SPEC)  // (SPEC frames read the lists, and keep them)
                 for (int q = 0; q < kPixelClasses; ++q) atomicExch(A.pl_rcnt + q, 0);
         }
     }

@@ -30,7 +30,7 @@ _U64P = C.POINTER(C.c_uint64)
 # ---- the hooks -----------------------------------------------------------------------------------
 def dedup_counts(reset=True):
     """(leaf children tested, leaf children dropped untested by a repeat mask, the build's
-    ORT_LEAF_DEDUP) of the host's non-counting camera walks since the last reset."""
+    Masks64::kLeafDedup) of the host's non-counting camera walks since the last reset."""
     lib = L.analysis_lib()
     lib.ort_debug_leaf_dedup.restype = C.c_int
     lib.ort_debug_leaf_dedup.argtypes = [_U64P, C.c_int32]

@@ -21,7 +21,7 @@ def _build_dedups():
 
 
 def test_build_has_repeat_masks():
-    """The default build ships the skip (ORT_LEAF_DEDUP 1 or 2): everything below relies on it."""
+    """The build ships the skip (Masks64::kLeafDedup, reported as 1): everything below relies on it."""
     assert _build_dedups() in (1, 2)
 
 

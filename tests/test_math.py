@@ -126,7 +126,7 @@ def test_kernel_closed_form_orders_match_shader_tables(ort):
 
 def test_rank_lut_is_a_bit_permutation(ort):
     """fast_step folds the rejected-sphere skip into the child mask before its one rank-LUT read
-    (render_core.h, ORT_KID_SKIP_FOLD): lut[c & ~s] == lut[c] & ~lut[s] for every child mask c
+    (render_core.h fast_visit): lut[c & ~s] == lut[c] & ~lut[s] for every child mask c
     and skip mask s, which holds because each LUT row maps octant bits to rank bits one for one."""
     import ctypes as C
 

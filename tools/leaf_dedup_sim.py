@@ -3,8 +3,9 @@ per-lane step records of sampled 8x8 primary-ray blocks under walk_sim's schedul
 internal-node block every iteration, the leaf-children loop as long as any lane has a surviving
 leaf child, the sphere loop as long as any lane has a sphere -- once from the counting walk (every
 surviving leaf child tested: the walk without masks) and once from the non-counting walk of the
-library loaded, whose leaf_kids drops what its masks name (ORT_LEAF_DEDUP of that build: run the
-tool once per variant library, ORT_LIB=build/ab/lib<variant>.so, for the table's rows).
+library loaded, whose leaf_kids drops what repeat mask A names (the variant ort_debug_leaf_dedup
+reports: 1; the builds without masks and with masks A and B, the table's other rows in
+profiles/leaf_dedup/ab.md, existed up to commit 83a4824).
 Prints per ray the steps, leaf-child visits and sphere tests, and per 64-lane block the leaf-loop
 trips and the model's VALU, with the walk's own totals from ort_debug_leaf_dedup beside them.
 usage: [ORT_LIB=<analysis library>] python tools/leaf_dedup_sim.py [config] [block_step]"""
@@ -90,7 +91,7 @@ def main():
     lens, steps, (tested, dropped, variant) = walk(1)
     got = replay(lens, steps, variant)
     print(f"{cfg}: {base['blocks']} blocks, {base['rays']} walking rays (every {step}th 8x8 block)")
-    for name, r in (("no masks (the counting walk)", base), (f"ORT_LEAF_DEDUP={variant} (this library)", got)):
+    for name, r in (("no masks (the counting walk)", base), (f"repeat masks, variant {variant} (this library)", got)):
         print(f"{name:36s} per ray: {r['steps']:.1f} steps, {r['visits']:.2f} leaf-child visits, {r['tests']:.2f} sphere tests; "
               f"per block: {r['trips']:.1f} leaf-loop trips, model VALU {r['valu']:,.0f} "
               f"({100 * (r['valu'] / base['valu'] - 1):+.1f} %)")
