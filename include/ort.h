@@ -628,7 +628,7 @@ int ort_accum_free(ort_ctx* ctx, ort_accum* accum);
  * reserved != 0, pointers that are not 4-byte aligned, an accumulation of another context,
  * samples_done == 0, variance on an accumulation without ORT_ACCUM_MOMENTS.  ORT_ERR_NO_SCENE after
  * a scene change, as for a pass.  Not in scope: moments on an ort_group, in ort_render or in the
- * per-bounce pipeline; sample counts driven by the variance. */
+ * per-bounce pipeline.  (Sample counts driven by the variance: adaptive accumulations, below.) */
 #define ORT_ACCUM_MOMENTS 1   /* the passes keep m2, the sum of the samples' squared luminances */
 int ort_accum_begin_ex(ort_ctx* ctx, const ort_params* params, const ort_tile* tile, int32_t flags, ort_accum** out);
 typedef struct ort_accum_moments {
@@ -638,6 +638,84 @@ typedef struct ort_accum_moments {
     int32_t reserved[3]; /* 0 */
 } ort_accum_moments;
 int ort_accum_read_moments(ort_ctx* ctx, ort_accum* accum, const ort_accum_moments* moments, void* stream);
+
+/* ---- adaptive sampling: passes that skip converged pixels --------------------------------------
+ * ort_accum_begin_ex with ORT_ACCUM_ADAPTIVE (it implies ORT_ACCUM_MOMENTS) begins an accumulation
+ * that keeps one more plane per path slot: an int32 count of the samples that pixel holds (28 bytes
+ * a slot instead of 24).  flags == 0 and flags == ORT_ACCUM_MOMENTS stay what they are: state,
+ * device_bytes, kernels.  A pixel's chain depends on the pixel alone, so a pixel that holds k samples
+ * holds, bit for bit, the sums, m2 and RNG state of a moments accumulation after k uniform samples;
+ * which pixel holds which count depends only on the sequence of the passes' parameters, never on
+ * scheduling, options or layout.
+ *   decision  once per pixel per pass, at the pass's start, from the pixel's stored state alone; N is
+ *             num_samples, k the pixel's count.  k >= N: held.  Otherwise k < min_samples or
+ *             threshold == 0: traced.  Otherwise with (mean, variance) as ort_accum_read_moments
+ *             writes them for the pixel at k: variance < 0 (no estimate: k < 2, a non-finite sum):
+ *             traced; else, in float32, one operation each,
+ *                 L   = (0.2126f * mean.x + 0.7152f * mean.y) + 0.0722f * mean.z
+ *                 ref = L > luminance_floor ? L : luminance_floor;   tol = threshold * ref
+ *             and the pixel is held iff variance <= tol * tol: the standard error of the mean
+ *             luminance is within `threshold` of it (of luminance_floor where the pixel is darker).
+ *   traced    the pixel runs samples k .. min(k + n_samples, N) - 1 of its chain -- the same RNG
+ *             chain, the strata of N, col += c, m2 as a moments pass -- and stores its state, sums
+ *             and new count.
+ *   held      nothing is traced and the pixel's state is untouched.
+ *   preview   with a non-NULL output every pixel of the tile is written, held or traced:
+ *             pow(sum / k, 1/2.2) with the pixel's own k, in every ort_output ort_accum_render takes;
+ *             padding rows as a pass writes them.
+ * On an adaptive accumulation the rest of ort_accum_* reads as follows.  ort_accum_render(n) is
+ * ort_accum_render_adaptive with {n, 0, 0.0f, any floor}: driven by it alone the accumulation is a
+ * moments accumulation bit for bit (previews, the finished frame, moments).  samples_done is the
+ * largest count a pixel can have, min(N, sum of the passes' n_samples), no longer "every pixel has
+ * this many": pixels may sit below N when it equals N, so a pass always launches (a tile of no
+ * pixels still launches nothing) and the finished frame is never served from the stored sums alone.
+ * ort_accum_read_moments uses each pixel's own k for mean and variance.  ort_accum_restart resets
+ * the counts with the sums (nothing allocated, launched or waited for: the next pass ignores the
+ * stored counts).  Scene changes, isolation, streams, host staging (counted in device_bytes, as is
+ * the list of pixels to trace that a pass with a criterion builds: 4 bytes a slot, from the first such pass on),
+ * several accumulations at once and the per-pass options (the same counts and state under every
+ * value) hold as for any accumulation.
+ * ort_accum_read_counts writes the counts: tight int32, one per tile pixel, in ort_accum_read_moments'
+ * index order; rows with y >= height get 0.  ort_accum_adaptive_stats is synchronous (a small device
+ * reduction and the readback of one record): over the tile pixels inside the frame, their number,
+ * the sum and the extremes of their counts, and `pending`, the pixels a pass with *criterion would
+ * trace now -- the loop of a camera at rest ends when pending == 0.  With no pixel inside the frame
+ * min_count and max_count are 0.  The call takes no stream: it runs on the context's own stream (which
+ * does not wait for other streams) and returns when the record is read.  Passes queued on a caller's
+ * stream must have finished before it is called -- it would read counts that are still being written
+ * and the loop's stop condition would be wrong; passes given no stream have finished when they return.
+ * ORT_ERR_INVALID_ARG, before anything is launched and with state and outputs untouched: NULL
+ * arguments, an accumulation that is not adaptive (these three calls), n_samples < 1,
+ * min_samples < 0, a negative or NaN threshold (+inf is valid: whatever has an estimate is held), a
+ * luminance_floor that is not finite and positive, reserved != 0, counts not 4-byte aligned, an output
+ * ort_render_ex refuses, an accumulation of another context.  ORT_ERR_NO_SCENE and
+ * ORT_ERR_UNSUPPORTED as for ort_accum_begin and ort_accum_render.
+ * Known limit: a pixel stopped at k < N has only covered the first k strata of N (glsl:647-652), so
+ * its estimate is not the stratified one a k-sample frame would give.  Not in scope: adaptive passes
+ * on an ort_group, in ort_render or in the per-bounce pipeline; a decision after every sample
+ * inside a pass. */
+/* (4, not 2: ort_accum_begin_ex has refused flags == 2 as an unknown bit since ORT_ACCUM_MOMENTS came,
+ * and callers written against that build keep that answer.) */
+#define ORT_ACCUM_ADAPTIVE 4  /* per-pixel sample counts; implies ORT_ACCUM_MOMENTS */
+typedef struct ort_accum_adaptive {      /* 32 bytes */
+    int32_t n_samples;        /* >= 1: a traced pixel gets min(n_samples, N - k) more samples in this pass */
+    int32_t min_samples;      /* >= 0: a pixel with k < min_samples is always traced */
+    float   threshold;        /* >= 0: relative standard error of the mean luminance; 0: never held */
+    float   luminance_floor;  /* > 0, finite: the luminance below which the error is taken absolute */
+    int32_t reserved[4];      /* 0 */
+} ort_accum_adaptive;
+int ort_accum_render_adaptive(ort_ctx* ctx, ort_accum* accum, const ort_accum_adaptive* pass, const ort_output* output,
+                              void* stream);
+int ort_accum_read_counts(ort_ctx* ctx, ort_accum* accum, int32_t* counts, int32_t on_device, void* stream);
+/* (A struct tag only: the record shares its name with the call, which C allows for a tag and not
+ * for a typedef name.  Write `struct ort_accum_adaptive_stats`, in C and in C++.) */
+struct ort_accum_adaptive_stats {        /* 40 bytes */
+    int64_t pixels, samples, pending;
+    int32_t min_count, max_count;
+    int32_t reserved[2];
+};
+int ort_accum_adaptive_stats(ort_ctx* ctx, ort_accum* accum, const ort_accum_adaptive* criterion,
+                             struct ort_accum_adaptive_stats* out);
 
 /* ---- several GPUs, one process --------------------------------------
  * The reference renders on one GL context; a caller of Raytracer::render() reaches the 8-GPU

@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = (
     "ort_trace_radiance",
     "ort_denoise", "ort_last_denoise_ms",
     "ort_accum_begin_ex", "ort_accum_read_moments", "ort_denoise_ex",
+    "ort_accum_render_adaptive", "ort_accum_read_counts", "ort_accum_adaptive_stats",
 )
 ORT_GROUP_TRANSPORT_RCCL = 0
 ORT_GROUP_TRANSPORT_COPY = 1
@@ -102,6 +103,7 @@ ORT_DENOISE_SAME_SPHERE = 1
 ORT_DENOISE_GAMMA = 2  # ort_denoise_ex only
 # ort_accum_begin_ex flags
 ORT_ACCUM_MOMENTS = 1
+ORT_ACCUM_ADAPTIVE = 4  # implies ORT_ACCUM_MOMENTS (2 stays an unknown bit)
 
 
 class OrtParams(C.Structure):
@@ -178,6 +180,16 @@ class OrtAccumMoments(C.Structure):
     _fields_ = [("mean", C.c_void_p), ("variance", C.c_void_p), ("on_device", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class OrtAccumAdaptive(C.Structure):
+    _fields_ = [("n_samples", C.c_int32), ("min_samples", C.c_int32), ("threshold", C.c_float),
+                ("luminance_floor", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+class OrtAccumAdaptiveStats(C.Structure):
+    _fields_ = [("pixels", C.c_int64), ("samples", C.c_int64), ("pending", C.c_int64), ("min_count", C.c_int32),
+                ("max_count", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class OrtSceneInfo(C.Structure):
     _fields_ = [
         ("n_spheres", C.c_int32), ("n_nodes", C.c_int32), ("n_indices", C.c_int64),
@@ -238,6 +250,13 @@ def _declare(lib, debug: str = "none"):
         "ort_debug_emulate_moments": (C.c_int, [_fp, _fp, _fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip,
                                                 C.c_int64, C.c_int32, C.POINTER(OrtParams), C.POINTER(OrtTile),
                                                 C.c_int32, _fp, _fp]),
+        "ort_accum_render_adaptive": (C.c_int, [_vp, _vp, C.POINTER(OrtAccumAdaptive), C.POINTER(OrtOutput), _vp]),
+        "ort_accum_read_counts": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp]),
+        "ort_accum_adaptive_stats": (C.c_int, [_vp, _vp, C.POINTER(OrtAccumAdaptive), C.POINTER(OrtAccumAdaptiveStats)]),
+        "ort_debug_emulate_adaptive": (C.c_int, [_fp, _fp, _fp, C.c_int32, _fp, _fp, _ip, _ip, _ip, C.c_int32, _ip,
+                                                 C.c_int64, C.c_int32, C.POINTER(OrtParams), C.POINTER(OrtTile),
+                                                 C.POINTER(OrtAccumAdaptive), C.c_int32, _ip, _fp, _fp]),
+        "ort_debug_adaptive_decision": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(OrtAccumAdaptive), _fp, C.c_float]),
         "ort_accum_begin": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(_vp)]),
         "ort_accum_render": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(OrtOutput), _vp]),
         "ort_accum_restart": (C.c_int, [_vp, _vp, C.POINTER(OrtParams)]),
@@ -307,7 +326,8 @@ def _declare(lib, debug: str = "none"):
             continue
         if name in ("ort_trace_camera", "ort_trace_rays_ex", "ort_trace_radiance", "ort_denoise",
                     "ort_last_denoise_ms", "ort_accum_begin_ex", "ort_accum_read_moments",
-                    "ort_denoise_ex") and debug == "present" and not hasattr(lib, name):
+                    "ort_denoise_ex", "ort_accum_render_adaptive", "ort_accum_read_counts",
+                    "ort_accum_adaptive_stats") and debug == "present" and not hasattr(lib, name):
             continue  # an ORT_LIB override of a build from before these calls (A/B runs): calling it raises
         f = getattr(lib, name)
         f.restype = res

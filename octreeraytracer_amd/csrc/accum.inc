@@ -44,6 +44,10 @@ hipError_t launch_accum_paths(int device, int mode, bool deep, bool lds_scene, s
 // accum_moments.inc so that those kernels follow every other one.
 hipError_t launch_accum_moments_paths(int device, int mode, bool deep, bool lds_scene, size_t lds, long long needed,
                                       const PipeArgs& a, hipStream_t s);
+// ... and for an adaptive one: ort_pixel_paths<..., 5>, named in adaptive.inc, after those.
+hipError_t launch_accum_adaptive_paths(int device, int mode, bool deep, bool lds_scene, size_t lds, long long needed,
+                                       const PipeArgs& a, hipStream_t s);
+void launch_adaptive_list(const PipeArgs& a, size_t slots, hipStream_t s);
 
 // The walk an accumulation of params p takes on ctx's scene (0 compact, 2 brute force), or the
 // refusal: what the whole-pixel kernel does not exist for.
@@ -65,7 +69,7 @@ bool accum_known(const ort_ctx* ctx, const ort_accum* acc) {
 
 int accum_begin_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int flags, ort_accum** out) {
     *out = nullptr;
-    if (flags & ~ORT_ACCUM_MOMENTS) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_accum_begin_ex: unknown flag bits");
+    if (flags & ~(ORT_ACCUM_MOMENTS | ORT_ACCUM_ADAPTIVE)) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_accum_begin_ex: unknown flag bits");
     const std::string bad = check_params(p, t);
     if (!bad.empty()) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_accum_begin: " + bad);
     int mode = 0, rc;
@@ -79,12 +83,13 @@ int accum_begin_impl(ort_ctx* ctx, const ort_params* p, const ort_tile* t, int f
     acc->p = *p;
     acc->t = *t;
     acc->mode = mode;
-    acc->moments = (flags & ORT_ACCUM_MOMENTS) != 0;
+    acc->adaptive = (flags & ORT_ACCUM_ADAPTIVE) != 0;
+    acc->moments = acc->adaptive || (flags & ORT_ACCUM_MOMENTS) != 0;
     acc->blocks = blocks;
     acc->scene_gen = ctx->scene.scene_gen;
     const size_t slots = (size_t)blocks * kBlock;
     hipError_t e = hipSuccess;
-    if ((rc = ensure(ctx, acc->state, std::max<size_t>((acc->moments ? 24 : 20) * slots, 16))) || (rc = ensure(ctx, acc->sync, 64)) ||
+    if ((rc = ensure(ctx, acc->state, std::max<size_t>((acc->adaptive ? 28 : acc->moments ? 24 : 20) * slots, 16))) || (rc = ensure(ctx, acc->sync, 64)) ||
         (e = acc->ev.create()) != hipSuccess) {
         if (!rc) rc = hip_fail(ctx, e, "ort_accum_begin: events");
         free_accum(acc);
@@ -112,7 +117,10 @@ int accum_restart_impl(ort_ctx* ctx, ort_accum* acc, const ort_params* p) {
     return ORT_OK;
 }
 
-int accum_render_impl(ort_ctx* ctx, ort_accum* acc, int n_samples, const ort_output* o, void* stream) {
+// ad: the criterion of a pass on an adaptive accumulation (ort_accum_render_adaptive, checked there), or
+// NULL: ort_accum_render, which on an adaptive accumulation traces every pixel below N.
+int accum_render_impl(ort_ctx* ctx, ort_accum* acc, int n_samples, const ort_output* o, void* stream,
+                      const ort_accum_adaptive* ad = nullptr) {
     if (n_samples < 1) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_accum_render: n_samples must be at least 1");
     const ort_params* p = &acc->p;
     const ort_tile* t = &acc->t;
@@ -159,12 +167,34 @@ int accum_render_impl(ort_ctx* ctx, ort_accum* acc, int n_samples, const ort_out
     a.fx_col = (float*)((char*)acc->state.p + sizeof(float2) * slots);
     a.sample = s0;
     a.sp_chunk = s1;
+    if (acc->adaptive) {  // (adaptive.inc: the pass's samples and the criterion, in fields no whole-pixel pass reads)
+        a.sp_nch = std::min(n_samples, N);
+        a.hcap = ad ? std::min(ad->min_samples, N) : 0;
+        a.gthr[0] = ad ? ad->threshold : 0.0f;
+        a.gthr[1] = ad ? ad->luminance_floor : 1.0f;
+        // a criterion that may hold pixels: the pre-pass lists the slots to trace and writes the others'
+        // preview; else -- threshold 0, or no pixel can have min_samples yet (no count exceeds s0) --
+        // every pixel below N is traced, in tile order, which keeps neighbouring blocks together
+        // (DESIGN.md 4.16 (b)).  The list's length lives after the list, in a cache line of its own:
+        // the cursor's line is under every wave's atomics
+        if (ad && ad->threshold != 0.0f && s0 != 0 && s0 >= ad->min_samples) {
+            if ((rc = ensure(ctx, acc->alist, 4 * slots + 256))) return rc;
+            a.fx_slot = (int*)acc->alist.p;
+            a.fx_n = (int*)((char*)acc->alist.p + 4 * slots + 128);
+        }
+    }
     HIPCHK(ctx, acc->ev.begin(s));
-    if (s1 > s0) {
+    if (s1 > s0 || acc->adaptive) {  // (adaptive: some pixels may sit below N whatever the passes' sum)
         HIPCHK(ctx, hipMemsetAsync(acc->sync.p, 0, 64, s));
         bool lds_scene;
         const size_t lds = pixel_paths_lds(ctx, acc->mode, a, lds_scene);
-        const hipError_t e = (acc->moments ? launch_accum_moments_paths : launch_accum_paths)(
+        if (a.fx_slot) {
+            HIPCHK(ctx, hipMemsetAsync(a.fx_n, 0, 4, s));
+            launch_adaptive_list(a, slots, s);
+            const hipError_t el = hipGetLastError();
+            if (el != hipSuccess) return hip_fail(ctx, el, "ort_accum_adaptive_list launch");
+        }
+        const hipError_t e = (acc->adaptive ? launch_accum_adaptive_paths : acc->moments ? launch_accum_moments_paths : launch_accum_paths)(
             ctx->device, acc->mode, ctx->scene.depth > 8, lds_scene, lds, acc->blocks, a, s);
         if (e != hipSuccess) return hip_fail(ctx, e, "ort_pixel_paths (accumulation pass) launch");
         acc->done = s1;
@@ -208,7 +238,8 @@ int ort_accum_get_info(const ort_accum* accum, ort_accum_info* info) {
     if (!accum || !info) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_accum_get_info: null argument");
     info->samples_done = accum->done;
     info->samples_total = accum->p.num_samples;
-    info->device_bytes = (int64_t)(accum->state.bytes + accum->sync.bytes + accum->stage.bytes + accum->mstage.bytes);
+    info->device_bytes = (int64_t)(accum->state.bytes + accum->sync.bytes + accum->stage.bytes + accum->mstage.bytes +
+                                     accum->astage.bytes + accum->alist.bytes);
     return ORT_OK;
 }
 

@@ -63,6 +63,10 @@ hipError_t launch_accum_moments_paths(int device, int mode, bool deep, bool lds_
     return hipGetLastError();
 }
 
+// The resolve of an adaptive accumulation (adaptive.inc, after every kernel of this file): a.sample != 0
+// says the stored counts are valid; mean, variance and counts: NULL, or tight planes of the tile.
+void launch_adaptive_resolve(const PipeArgs& a, size_t slots, float* mean, float* variance, int32_t* counts, hipStream_t s);
+
 int accum_read_moments_impl(ort_ctx* ctx, ort_accum* acc, const ort_accum_moments* m, void* stream) {
     const char* who = "ort_accum_read_moments: ";
     if (!m->mean && !m->variance) return fail(ctx, ORT_ERR_INVALID_ARG, std::string(who) + "mean and variance are both NULL");
@@ -102,7 +106,11 @@ int accum_read_moments_impl(ort_ctx* ctx, ort_accum* acc, const ort_accum_moment
 #endif
     a.fx_col = (float*)((char*)acc->state.p + sizeof(float2) * slots);
     a.sp_chunk = acc->done;
-    hipLaunchKernelGGL(ort_accum_moments_resolve, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, a, d_mean, d_var);
+    a.sample = acc->done;
+    if (acc->adaptive)  // each pixel at its own count (adaptive.inc)
+        launch_adaptive_resolve(a, slots, d_mean, d_var, nullptr, s);
+    else
+        hipLaunchKernelGGL(ort_accum_moments_resolve, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, a, d_mean, d_var);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(ctx, e, "ort_accum_moments_resolve launch");
     if (host) {

@@ -373,12 +373,15 @@ struct ort_accum {
     int mode = 0;          // 0 the compact layout's walk, 2 brute force
     int done = 0;
     bool moments = false;  // ORT_ACCUM_MOMENTS: the state carries the m2 plane
+    bool adaptive = false; // ORT_ACCUM_ADAPTIVE (implies moments): ... and an int plane, each pixel's count; done is the largest one possible
     long long blocks = 0;  // 16x16 tiles
     unsigned long long scene_gen = 0;
-    DevBuf state;          // float2[slots] | float[3][slots] (| float[slots]: m2)
+    DevBuf state;          // float2[slots] | float[3][slots] (| float[slots]: m2 (| int[slots]: counts))
     DevBuf sync;           // the launch's cursor and done count (16 ints, zeroed before every pass)
     DevBuf stage;          // host output: the tight picture on the device (allocated by the first such pass)
     DevBuf mstage;         // ort_accum_read_moments into host memory: the mean and the variance, tight
+    DevBuf alist;          // adaptive: the slots a pass traces, listed by its pre-pass (allocated by the first pass that may hold pixels)
+    DevBuf astage;         // adaptive: ort_accum_read_counts into host memory, and the stats reduction's records
     EventPair ev;
 };
 
@@ -422,6 +425,8 @@ void free_accum(ort_accum* a) {
     free_buf(a->sync);
     free_buf(a->stage);
     free_buf(a->mstage);
+    free_buf(a->astage);
+    free_buf(a->alist);
     a->ev.destroy();
     delete a;
 }

@@ -125,6 +125,22 @@ int ort_debug_emulate_moments(const float* sphere_center_radius, const float* sp
                               const int32_t* object_indices, int64_t n_indices, int32_t layout,
                               const ort_params* params, const ort_tile* tile, int32_t samples_done,
                               float* mean, float* variance);
+// TEST-ONLY: an adaptive accumulation (ort_accum_render_adaptive) of params and tile driven by the
+// n_passes passes of `passes`, on the host CPU: per pixel the shared decision (adaptive.inc's
+// adaptive_traces) on shade_pixel's chain at the pixel's count.  ort_debug_emulate_moments' scene
+// arguments; counts (1 int per tile pixel), mean and variance as ort_accum_read_counts and
+// ort_accum_read_moments write them afterwards, each may be NULL.
+int ort_debug_emulate_adaptive(const float* sphere_center_radius, const float* sphere_mat_albedo,
+                               const float* sphere_fuzz_ri, int32_t n_spheres, const float* node_min,
+                               const float* node_max, const int32_t* children_offset,
+                               const int32_t* objects_offset, const int32_t* object_count, int32_t n_nodes,
+                               const int32_t* object_indices, int64_t n_indices, int32_t layout,
+                               const ort_params* params, const ort_tile* tile, const ort_accum_adaptive* passes,
+                               int32_t n_passes, int32_t* counts, float* mean, float* variance);
+// TEST-ONLY: the shared decision itself for one pixel's stored state: 1 traced, 0 held (k the
+// pixel's count, n_total the target N, col the colour sum, m2 the sum of squared luminances), or
+// -1 where ort_accum_render_adaptive refuses the criterion.
+int ort_debug_adaptive_decision(int32_t k, int32_t n_total, const ort_accum_adaptive* criterion, const float* col, float m2);
 // ANALYSIS-ONLY: lane overlap of sampled 8x8 primary-ray blocks (tools/wave_stats.py).
 int ort_debug_wave_stats(const float* sphere_center_radius, const float* sphere_mat_albedo,
                          const float* sphere_fuzz_ri, int32_t n_spheres, const float* node_min,

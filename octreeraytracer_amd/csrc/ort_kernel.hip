@@ -137,6 +137,9 @@ struct PipeArgs {
     // states; one with fx_slot runs the fixup list: pixel fx_slot[i] from sample fx_s0[i] with
     // state fx_st[i] and the colour sum of its earlier samples fx_col (three planes of total
     // floats), *fx_n entries
+    // (An adaptive pass, PM 5, and its pre-pass and stats kernels also borrow sp_nch, hcap and gthr[0..1]
+    // from further up -- adaptive.inc says for what: a whole-pixel kernel that starts to read those must
+    // look there first.)
     // An accumulation pass (ort_accum_render, PM 3: accum.inc) borrows four of these fields, indexed
     // by path slot: samples `sample` .. sp_chunk - 1 of every pixel, from the RNG state fx_st[k] and
     // the colour sum fx_col (three planes of total floats) when sample > 0, both stored back
@@ -1532,16 +1535,24 @@ __device__ __forceinline__ void block_account(const PipeArgs& A, int slot, int b
 // states and sums kept per slot between passes; instantiated there, after every kernel of this file),
 // 4 a pass that also keeps the slot's second luminance moment m2 (accum_moments.inc, after every other
 // kernel): the plane after the three colour-sum planes, read, added to and written at each sample's
-// end -- sample ends are rare next to walk steps, and nothing more lives across the walk
+// end -- sample ends are rare next to walk steps, and nothing more lives across the walk,
+// 5 an adaptive pass (adaptive.inc, after every other kernel): a moments pass in which every pixel
+// starts at its own count, the int plane after m2, and only where adaptive_traces says so; its end
+// sample is recomputed at each sample's end from the still-unwritten count, as m2 is; with fx_slot it
+// takes its candidates from that list of *fx_n slots (the pre-pass listed the pixels to trace) instead
+// of the tile's blocks.  (The host sends it in tile order only where the decision can find nothing but
+// k >= N, and the pre-pass has decided for a list; the full decision stays at the refill all the same:
+// with the plain s >= ns test in its place the all-traced pass measured 4.5 % slower on stats114)
+ORT_FN bool adaptive_traces(int k, int N, int min_samples, float threshold, float luminance_floor, ort::V3 col, float m2);
 template <int MODE, bool DEEP, bool LDS, int PM = 0>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ORT_PIXEL_WAVES)))
 ort_pixel_paths(PipeArgs A) {
     constexpr bool SPEC = PM == 1;
-    constexpr bool PASS = PM == 3 || PM == 4;
+    constexpr bool PASS = PM == 3 || PM == 4 || PM == 5;
     // a SPEC launch in a fall-back frame, and the fixup launch's workgroups beyond what its list
     // needs, only count themselves out (before any LDS set-up)
     const bool idle_wg = (SPEC && A.sp_ctl[2] == 0) ||
-                         (PM == 2 && A.fx_slot && (long long)blockIdx.x * kBlock >= (long long)*A.fx_n + kBlock);
+                         ((PM == 2 || PM == 5) && A.fx_slot && (long long)blockIdx.x * kBlock >= (long long)*A.fx_n + kBlock);
     if (idle_wg) {
         if (threadIdx.x == 0 && atomicAdd(A.sync + 2, 1) == (int)gridDim.x - 1) {
             atomicExch(A.sync + 1, 0);
@@ -1575,8 +1586,10 @@ ort_pixel_paths(PipeArgs A) {
     // pairs, a block's samples one after another; the fixup list: 64 of its entries at a time.
     // Lane q < 32 holds the inclusive prefix of the class counts.
     const bool fixup = PM == 2 && A.fx_slot;
+    const bool alist = PM == 5 && A.fx_slot;  // an adaptive pass over the listed slots (adaptive.inc), 64 entries at a time
+    const int n_alist = alist ? *A.fx_n : 0;   // (read once: nothing appends during the pass)
     const int n_blocks = A.total >> 6;
-    const int n_items = SPEC ? n_blocks * A.sp_nch : (fixup ? (*A.fx_n + 63) >> 6 : n_blocks);
+    const int n_items = SPEC ? n_blocks * A.sp_nch : (fixup ? (*A.fx_n + 63) >> 6 : (alist ? (n_alist + 63) >> 6 : n_blocks));
     int cls_end = 0;
     if (A.pl_r) {
         cls_end = lane < kPixelClasses ? A.pl_rcnt[lane] : 0;
@@ -1622,9 +1635,9 @@ ort_pixel_paths(PipeArgs A) {
                 j = __shfl(j, 0);
                 if (j >= n_items) {
                     drained = true;
-                } else if (fixup) {
+                } else if (fixup || alist) {
                     next = j << 6;
-                    end = min(next + 64, *A.fx_n);
+                    end = min(next + 64, alist ? n_alist : *A.fx_n);
                 } else {  // SPEC: block j / nch (its pixels' chunk j % nch), heavy blocks first as well
                     const int jb = SPEC ? j / A.sp_nch : j;
                     int blk = jb;
@@ -1645,7 +1658,7 @@ ort_pixel_paths(PipeArgs A) {
                 if (k < 0) {
                     const int rank = __popcll(idle & below);
                     if (rank < take) {
-                        const int cand = fixup ? A.fx_slot[next + rank] : next + rank;
+                        const int cand = fixup || alist ? A.fx_slot[next + rank] : next + rank;
                         bool pixel = false;
                         int cx, cy;
                         if (slot_coords(A, cand, cx, cy)) {
@@ -1676,6 +1689,7 @@ ort_pixel_paths(PipeArgs A) {
                                     col = ort::mk(A.fx_col[e], A.fx_col[(size_t)A.total + e], A.fx_col[2 * (size_t)A.total + e]);
                                 } else if (PASS) {  // the pass's first sample, from the slot's stored state and sum
                                     s = A.sample;
+                                    if (PM == 5 && s != 0) s = (reinterpret_cast<const int*>(A.fx_col) + 4 * (size_t)A.total)[k];  // the pixel's own count
                                     if (s == 0) {
                                         ort::pixel_rng_init(A.pp, px, py, st);
                                         col = ort::mk(0.0f, 0.0f, 0.0f);
@@ -1690,7 +1704,14 @@ ort_pixel_paths(PipeArgs A) {
                                     s = 0;
                                     col = ort::mk(0.0f, 0.0f, 0.0f);
                                 }
-                                ray = ort::primary_ray(A.pp, px, py, s, st);
+                                if (PM == 5) {  // adaptive: held pixels only show their stored sum
+                                    const float m2 = s >= 2 ? A.fx_col[3 * (size_t)A.total + k] : 0.0f;
+                                    if (!adaptive_traces(s, ns, A.hcap, A.gthr[0], A.gthr[1], col, m2)) {
+                                        if (A.out) store_pixel(reread_args(A), cy, cx, py, ort::finish_pixel(col, s));
+                                        k = -1;
+                                    }
+                                }
+                                if (PM != 5 || k >= 0) ray = ort::primary_ray(A.pp, px, py, s, st);
                                 pixel = true;
                             } else if (PASS) {  // ... of an accumulation pass: with a picture only
                                 if (A.out) store_padding(reread_args(A), cy, cx);
@@ -1743,7 +1764,7 @@ ort_pixel_paths(PipeArgs A) {
                 }
             } else if (ended) {  // col += radiance(r) (glsl:655); the pixel's next sample, or its final colour
                 col = ort::add(col, c);
-                if (PM == 4) {  // m2 += l * l, l the sample's luminance (sample 0 starts it at 0)
+                if (PM == 4 || PM == 5) {  // m2 += l * l, l the sample's luminance (sample 0 starts it at 0)
                     const float l = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
                     float* m2 = A.fx_col + 3 * (size_t)A.total + k;
                     const float m = s == 0 ? 0.0f : *m2;
@@ -1751,7 +1772,13 @@ ort_pixel_paths(PipeArgs A) {
                 }
                 if (PM == 2 && A.sp_cur && ((s + 1) % A.sp_chunk == 0 || s + 1 == ns))  // a chunk's end state, for SPEC
                     A.sp_cur[(size_t)(s / A.sp_chunk) * A.total + k] = make_float2(st.x, st.y);
-                if (++s < (PASS ? A.sp_chunk : ns)) {
+                int s_end = PASS ? A.sp_chunk : ns;
+                if (PM == 5) {  // the pixel's own end: its count, unwritten until then, plus the pass's samples
+                    const PipeArgs R = reread_args(A);
+                    const int k0 = R.sample ? (reinterpret_cast<const int*>(R.fx_col) + 4 * (size_t)R.total)[k] : 0;
+                    s_end = min(k0 + R.sp_nch, ns);
+                }
+                if (++s < s_end) {
                     b = 0;
                     c = ort::mk(1.0f, 1.0f, 1.0f);
                     importance = 1.0f;
@@ -1761,6 +1788,7 @@ ort_pixel_paths(PipeArgs A) {
                     A.fx_col[k] = col.x;
                     A.fx_col[(size_t)A.total + k] = col.y;
                     A.fx_col[2 * (size_t)A.total + k] = col.z;
+                    if (PM == 5) (reinterpret_cast<int*>(A.fx_col) + 4 * (size_t)A.total)[k] = s;
                     const PipeArgs R = reread_args(A);
                     if (R.out) {
                         int cx, cy;
@@ -1968,3 +1996,8 @@ __global__ void __launch_bounds__(kBlock) k_cam_node(const uint2* node, const ui
     cam[i] = ort::cam_record(rec, ab);
 }
 }  // namespace
+
+// Adaptive accumulations (ORT_ACCUM_ADAPTIVE, ort_accum_render_adaptive, ort_accum_read_counts,
+// ort_accum_adaptive_stats): the ort_pixel_paths<..., 5> instances, the counts resolve and the stats
+// reduction, after accum_moments.inc and every other kernel.
+#include "adaptive.inc"

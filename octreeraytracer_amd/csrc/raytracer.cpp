@@ -246,7 +246,8 @@ int Raytracer::renderProgressive(const Camera& cam, int samples, float* rgb, int
     int rc = ORT_OK;
     if (!accum) {
         const ort_tile t{0, width, 0, height, 0, 0};
-        if ((rc = ort_accum_begin_ex(ctx, &p, &t, accumMoments ? ORT_ACCUM_MOMENTS : 0, &accum)) != ORT_OK) return rc;
+        const int flags = accumAdaptive ? ORT_ACCUM_ADAPTIVE : (accumMoments ? ORT_ACCUM_MOMENTS : 0);
+        if ((rc = ort_accum_begin_ex(ctx, &p, &t, flags, &accum)) != ORT_OK) return rc;
         accumParams = p;
     } else if (std::memcmp(p.view, accumParams.view, sizeof p.view) != 0 ||
                std::memcmp(p.camera_position, accumParams.camera_position, sizeof p.camera_position) != 0 ||
@@ -255,7 +256,12 @@ int Raytracer::renderProgressive(const Camera& cam, int samples, float* rgb, int
         accumParams = p;
     }
     const ort_output o = {rgb, 0, ORT_FORMAT_RGB32F, ORT_PLACE_TILE, 0, 0};
-    rc = ort_accum_render(ctx, accum, samples, &o, nullptr);
+    if (accumAdaptive) {
+        const ort_accum_adaptive a = adaptiveCriterion(samples);
+        rc = ort_accum_render_adaptive(ctx, accum, &a, &o, nullptr);
+    } else {
+        rc = ort_accum_render(ctx, accum, samples, &o, nullptr);
+    }
     ort_accum_info info{};
     if (samplesDone && ort_accum_get_info(accum, &info) == ORT_OK) *samplesDone = info.samples_done;
     return rc;
@@ -266,6 +272,34 @@ void Raytracer::setProgressiveMoments(bool on) {
     accumMoments = on;
     if (accum && ctx) (void)ort_accum_free(ctx, accum);  // the state has another shape: the frame starts again
     accum = nullptr;
+}
+
+ort_accum_adaptive Raytracer::adaptiveCriterion(int samples) const {
+    return {samples, adaptiveMinSamples, adaptiveThreshold, adaptiveFloor, {0, 0, 0, 0}};
+}
+
+void Raytracer::setProgressiveAdaptive(bool on, float threshold, int minSamples, float luminanceFloor) {
+    adaptiveThreshold = threshold;
+    adaptiveMinSamples = minSamples;
+    adaptiveFloor = luminanceFloor;
+    if (on == accumAdaptive) return;  // (a new criterion alone applies from the next pass on)
+    accumAdaptive = on;
+    if (accum && ctx) (void)ort_accum_free(ctx, accum);  // the state has another shape: the frame starts again
+    accum = nullptr;
+}
+
+int Raytracer::readSampleCounts(int32_t* counts, bool onDevice) {
+    if (group) return ORT_ERR_UNSUPPORTED;
+    if (!ctx || !accum) return ORT_ERR_INVALID_ARG;  // no renderProgressive yet
+    return ort_accum_read_counts(ctx, accum, counts, onDevice ? 1 : 0, nullptr);
+}
+
+long long Raytracer::pendingPixels() {
+    if (group || !ctx || !accum || !accumAdaptive) return -1;
+    const ort_accum_adaptive a = adaptiveCriterion(1);
+    struct ort_accum_adaptive_stats st;
+    if (ort_accum_adaptive_stats(ctx, accum, &a, &st) != ORT_OK) return -1;
+    return (long long)st.pending;
 }
 
 int Raytracer::readMoments(float* mean, float* variance, bool onDevice) {

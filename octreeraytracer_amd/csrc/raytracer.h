@@ -160,6 +160,19 @@ public:
     int denoise(const Camera& cam, const ort_tile& tile, const float* rgb, const float* variance, float sigmaVariance,
                 bool gamma, const ort_output& output, const DenoiseOptions& options = {});
 
+    // Adaptive sampling (include/ort.h ort_accum_render_adaptive): with setProgressiveAdaptive(true, ...)
+    // renderProgressive's accumulation keeps a sample count per pixel (and the moments; the switch
+    // starts the accumulation again) and each call traces `samples` more samples only of the pixels
+    // that hold fewer than minSamples or whose mean luminance's standard error is still above
+    // threshold x max(luminance, luminanceFloor); every pixel is shown at its own count, and
+    // samplesDone is then the largest count a pixel can have.  readSampleCounts writes width *
+    // height counts (host memory or, with onDevice, device memory); pendingPixels is the number of
+    // pixels the next call would trace (-1: no adaptive accumulation yet, or an error) -- the loop of
+    // a camera at rest ends when it is 0.  readMoments gives every pixel's mean and variance at its own count.
+    void setProgressiveAdaptive(bool on, float threshold = 0.02f, int minSamples = 4, float luminanceFloor = 0.05f);
+    int readSampleCounts(int32_t* counts, bool onDevice = false);
+    long long pendingPixels();
+
     Camera camera;  // the reference keeps a global Camera (src/main.cpp:18); pose set like main()
     const RaytracerConfig& config() const { return cfg; }
     const std::vector<Sphere>& getSpheres() const { return spheres; }
@@ -202,6 +215,10 @@ private:
     ort_accum* accum = nullptr;    // renderProgressive's accumulation (the context owns it) and its camera
     ort_params accumParams{};
     bool accumMoments = false;     // setProgressiveMoments
+    bool accumAdaptive = false;    // setProgressiveAdaptive and its criterion
+    float adaptiveThreshold = 0.02f, adaptiveFloor = 0.05f;
+    int adaptiveMinSamples = 4;
+    ort_accum_adaptive adaptiveCriterion(int samples) const;
     double gpuBuildSeconds = 0.0;
     StatsWork work;               // counted after the timed frames when cfg.extendedStats
 

@@ -335,13 +335,17 @@ class Renderer:
         return o, out
 
     # -- progressive frames -----------------------------------------------------------
-    def accumulate(self, params: FrameParams, tile: Tile | None = None, moments: bool = False) -> "Accumulation":
+    def accumulate(self, params: FrameParams, tile: Tile | None = None, moments: bool = False,
+                   adaptive: bool = False) -> "Accumulation":
         """Begin accumulating the frame `params` (its num_samples is the target N) over several
         calls: ort_accum_begin (include/ort.h).  Allocates the per-pixel state, traces nothing.
         moments: the passes also keep each pixel's sum of squared sample luminances (ort_accum_begin_ex
         with ORT_ACCUM_MOMENTS, 4 bytes more per path slot), which ``Accumulation.moments`` turns
-        into a per-pixel variance; the pictures are the same bit for bit."""
-        return Accumulation(self, params, tile or Tile.full(params), moments)
+        into a per-pixel variance; the pictures are the same bit for bit.
+        adaptive: ORT_ACCUM_ADAPTIVE (it implies moments, 4 bytes more again): every pixel keeps its
+        own sample count, and ``Accumulation.step_adaptive`` traces only the pixels whose mean is
+        still noisy; ``step`` traces them all, as on a moments accumulation."""
+        return Accumulation(self, params, tile or Tile.full(params), moments, adaptive)
 
     # -- ray queries ------------------------------------------------------------------
     def _device_arg(self, who, x, what, dtype_name, need):
@@ -803,15 +807,17 @@ class Accumulation:
     A context manager: leaving it frees the state (as ``close`` does; the renderer's ``close``
     frees what is left)."""
 
-    def __init__(self, renderer: Renderer, params: FrameParams, tile: Tile, moments: bool = False):
+    def __init__(self, renderer: Renderer, params: FrameParams, tile: Tile, moments: bool = False, adaptive: bool = False):
         self._r = renderer
         self._h = C.c_void_p()
         self.params, self.tile = params, tile
-        self.keeps_moments = bool(moments)
+        self.is_adaptive = bool(adaptive)
+        self.keeps_moments = bool(moments) or self.is_adaptive
         self._guides = None
         p, t = params.to_c(), tile.to_c()
-        if moments:
-            renderer._check(renderer._lib.ort_accum_begin_ex(renderer._ctx, C.byref(p), C.byref(t), L.ORT_ACCUM_MOMENTS,
+        if self.keeps_moments:
+            flags = L.ORT_ACCUM_ADAPTIVE if self.is_adaptive else L.ORT_ACCUM_MOMENTS
+            renderer._check(renderer._lib.ort_accum_begin_ex(renderer._ctx, C.byref(p), C.byref(t), flags,
                                                              C.byref(self._h)))
         else:
             renderer._check(renderer._lib.ort_accum_begin(renderer._ctx, C.byref(p), C.byref(t), C.byref(self._h)))
@@ -865,6 +871,66 @@ class Accumulation:
         o, out = r._output("step", self.params, self.tile, out, format, row_pitch, place)
         r._check(r._lib.ort_accum_render(r._ctx, self._h, int(n), C.byref(o), s))
         return out
+
+    @staticmethod
+    def _criterion(n, threshold, min_samples, luminance_floor):
+        a = L.OrtAccumAdaptive()
+        a.n_samples, a.min_samples = int(n), int(min_samples)
+        a.threshold, a.luminance_floor = float(threshold), float(luminance_floor)
+        return a
+
+    def step_adaptive(self, n: int = 1, threshold: float | None = None, min_samples: int | None = None,
+                      luminance_floor: float | None = None, out=None, stream=None, *,
+                      format: str = "rgb32f", row_pitch: int | None = None, place: str = "tile"):
+        """An adaptive pass (``accumulate(..., adaptive=True)``; ort_accum_render_adaptive in
+        include/ort.h): every pixel that holds fewer than min_samples samples, or whose mean
+        luminance's standard error is still above threshold x max(luminance, luminance_floor), gets
+        its next min(n, total - its count) samples; every other pixel is held, untouched.  The
+        picture shows every pixel at its own count.  threshold, min_samples, luminance_floor: None
+        takes DEFAULT_ADAPTIVE_*.  out, stream, format, row_pitch, place: as ``step``, which this
+        returns like."""
+        r = self._r
+        a = self._criterion(n, *_adaptive_defaults(threshold, min_samples, luminance_floor))
+        s = C.c_void_p(int(stream)) if stream else None
+        if out is False:
+            r._check(r._lib.ort_accum_render_adaptive(r._ctx, self._h, C.byref(a), None, s))
+            return None
+        o, out = r._output("step_adaptive", self.params, self.tile, out, format, row_pitch, place)
+        r._check(r._lib.ort_accum_render_adaptive(r._ctx, self._h, C.byref(a), C.byref(o), s))
+        return out
+
+    def counts(self, out=None, stream=None):
+        """The samples each pixel holds, int32 (rows, width), 0 in rows past the frame:
+        ort_accum_read_counts.  Returns a numpy array, or, given a torch CUDA tensor (or a device
+        pointer) as out, writes and returns that."""
+        r = self._r
+        rows, width = int(self.tile.rows), int(self.tile.width)
+        n = rows * width
+        s = C.c_void_p(int(stream)) if stream else None
+        if out is None or isinstance(out, np.ndarray):
+            if out is None:
+                out = np.empty((rows, width), np.int32)
+            if out.dtype != np.int32 or not out.flags.c_contiguous or out.size != n:
+                raise ValueError(f"counts: out must be a C-contiguous int32 array of {n} elements")
+            r._check(r._lib.ort_accum_read_counts(r._ctx, self._h, C.c_void_p(out.ctypes.data), 0, s))
+            return out
+        ptr = r._device_arg("counts", out, "out", "int32", 4 * n)
+        r._check(r._lib.ort_accum_read_counts(r._ctx, self._h, C.c_void_p(ptr), 1, s))
+        return out
+
+    def adaptive_stats(self, threshold: float | None = None, min_samples: int | None = None,
+                       luminance_floor: float | None = None, n: int = 1) -> dict:
+        """The counts in short (ort_accum_adaptive_stats, synchronous): the tile's pixels inside the
+        frame, the sum and the extremes of their counts, and pending: the pixels a ``step_adaptive``
+        with this criterion would trace now.  The loop of a camera at rest ends at pending == 0.
+        It takes no stream and runs on the renderer's own: passes queued with ``stream=`` must have
+        finished (synchronize that stream first), or it reads counts that are still being written."""
+        r = self._r
+        a = self._criterion(n, *_adaptive_defaults(threshold, min_samples, luminance_floor))
+        st = L.OrtAccumAdaptiveStats()
+        r._check(r._lib.ort_accum_adaptive_stats(r._ctx, self._h, C.byref(a), C.byref(st)))
+        return {"pixels": st.pixels, "samples": st.samples, "pending": st.pending, "min_count": st.min_count,
+                "max_count": st.max_count}
 
     def moments(self, mean: bool = True, variance: bool = True, out_mean=None, out_variance=None, stream=None):
         """The linear mean (rows, width, 3) of the samples done so far -- the picture before its gamma
@@ -941,6 +1007,19 @@ class Accumulation:
         ms = C.c_float()
         self._r._check(self._r._lib.ort_accum_last_pass_ms(self._r._ctx, self._h, C.byref(ms)))
         return ms.value
+
+
+# ``Accumulation.step_adaptive``'s defaults: a relative standard error of 2 % of the mean luminance, taken
+# absolute below a luminance of 0.05, never judged before 4 samples.
+DEFAULT_ADAPTIVE_THRESHOLD = 0.02
+DEFAULT_ADAPTIVE_MIN_SAMPLES = 4
+DEFAULT_ADAPTIVE_LUMINANCE_FLOOR = 0.05
+
+
+def _adaptive_defaults(threshold, min_samples, luminance_floor):
+    return (DEFAULT_ADAPTIVE_THRESHOLD if threshold is None else threshold,
+            DEFAULT_ADAPTIVE_MIN_SAMPLES if min_samples is None else min_samples,
+            DEFAULT_ADAPTIVE_LUMINANCE_FLOOR if luminance_floor is None else luminance_floor)
 
 
 # Reference-layout record bytes touched, SURVEY.md 8(d): the algorithmic traffic model.
@@ -1288,6 +1367,51 @@ def accum_moments_host(spheres: SphereSet, tree: FlatOctree | None, params: Fram
                                           C.byref(t), k, L.fptr(mean), L.fptr(var)))
     del keep
     return mean, var
+
+
+def accum_adaptive_host(spheres: SphereSet, tree: FlatOctree | None, params: FrameParams, tile: Tile | None = None,
+                        layout: int = L.ORT_LAYOUT_COMPACT, passes=()):
+    """TEST-ONLY: an adaptive accumulation driven by `passes` on the host CPU (ort_debug_emulate_adaptive:
+    the kernel's per-pixel code and the shared decision).  passes: (n_samples, min_samples, threshold,
+    luminance_floor) tuples.  Returns (counts (rows, width) int32, mean (rows, width, 3), variance
+    (rows, width)) as ``Accumulation.counts`` and ``Accumulation.moments`` return them afterwards."""
+    lib = L.analysis_lib()
+    tile = tile or Tile.full(params)
+    counts = np.empty((tile.rows, tile.width), np.int32)
+    mean = np.empty((tile.rows, tile.width, 3), np.float32)
+    var = np.empty((tile.rows, tile.width), np.float32)
+    p, t = params.to_c(), tile.to_c()
+    cr = np.ascontiguousarray(spheres.center_radius, np.float32)
+    ma = np.ascontiguousarray(spheres.mat_albedo, np.float32)
+    fr = np.ascontiguousarray(spheres.fuzz_ri, np.float32)
+    if tree is None:
+        keep = ()
+        args = (None, None, None, None, None, 0, None, 0)
+    else:
+        keep = tuple(np.ascontiguousarray(a, t_) for a, t_ in (
+            (tree.node_min, np.float32), (tree.node_max, np.float32), (tree.children_offset, np.int32),
+            (tree.objects_offset, np.int32), (tree.object_count, np.int32), (tree.object_indices, np.int32)))
+        args = (L.fptr(keep[0]), L.fptr(keep[1]), L.iptr(keep[2]), L.iptr(keep[3]), L.iptr(keep[4]),
+                tree.n_nodes, L.iptr(keep[5]), tree.n_indices)
+    passes = list(passes)
+    arr = (L.OrtAccumAdaptive * max(len(passes), 1))()
+    for a, (n, min_samples, threshold, floor) in zip(arr, passes):
+        a.n_samples, a.min_samples, a.threshold, a.luminance_floor = int(n), int(min_samples), float(threshold), float(floor)
+    L.acheck(lib.ort_debug_emulate_adaptive(L.fptr(cr), L.fptr(ma), L.fptr(fr), spheres.n, *args, layout, C.byref(p),
+                                           C.byref(t), arr, len(passes), L.iptr(counts), L.fptr(mean), L.fptr(var)))
+    del keep
+    return counts, mean, var
+
+
+def adaptive_decision_host(k: int, n_total: int, criterion, col, m2: float) -> int:
+    """TEST-ONLY: the shared decision for one stored pixel state (ort_debug_adaptive_decision): 1
+    traced, 0 held, -1 a refused criterion.  criterion: (n_samples, min_samples, threshold, floor)."""
+    lib = L.analysis_lib()
+    a = L.OrtAccumAdaptive()
+    a.n_samples, a.min_samples, a.threshold, a.luminance_floor = (int(criterion[0]), int(criterion[1]), float(criterion[2]),
+                                                                  float(criterion[3]))
+    c = np.ascontiguousarray(col, np.float32)
+    return int(lib.ort_debug_adaptive_decision(int(k), int(n_total), C.byref(a), L.fptr(c), C.c_float(m2)))
 
 
 def gamma_host(rgb):
