@@ -68,7 +68,13 @@ typedef struct ort_params {
  *     y = y0 + (j / band_height) * band_stride + (j % band_height)
  * (band_height <= 0 means one band: y = y0 + j).  Pixel rows are GL rows: y = 0 is the
  * BOTTOM row of the image.  Columns are x0 .. x0+width-1.  Rows with y >= height are
- * written as zeros.  The RNG seed and the camera always use the full-frame resolution,
+ * written as zeros.  The row limit: y0 >= 0, band_stride >= band_height, and the pixel row of
+ * the tile's last row (j = rows - 1, the largest: computed in 64 bits) is at most 2^31 - 1; a
+ * tile past it is refused with ORT_ERR_INVALID_ARG before anything is allocated or launched
+ * and the output is untouched.  The limit is INT_MAX itself, not INT_MAX - 15: the kernels lay
+ * the tile out in 16-row blocks, but every site that turns a slot's row into a pixel row does
+ * so only for rows j < rows (slot_coords' bound, or the row loop's).
+ * The RNG seed and the camera always use the full-frame resolution,
  * so any tiling produces the same pixels as a full-frame render.
  * A tile of no pixels (width == 0 or rows == 0) is valid: ort_render, ort_render_ex and
  * ort_count_traffic return ORT_OK without launching anything, the output is left untouched

@@ -25,6 +25,14 @@ std::string check_frame_tile(const ort_params* p, const ort_tile* t) {
     if (t->x0 < 0 || (int64_t)t->x0 + t->width > p->width) return "tile columns outside the frame";
     if (t->y0 < 0) return "negative y0";
     if (t->band_height > 0 && t->band_stride < t->band_height) return "band_stride < band_height";
+    // tile_row_to_y is 32-bit arithmetic: the pixel row of the tile's last row (the largest: rows
+    // grow with j) must be an int, or it would wrap negative and pass for a row of the frame
+    if (t->rows > 0) {
+        const int64_t j = (int64_t)t->rows - 1;
+        const int64_t last = t->band_height > 0 ? (int64_t)t->y0 + (j / t->band_height) * (int64_t)t->band_stride + j % t->band_height
+                                                : (int64_t)t->y0 + j;
+        if (last > 0x7fffffffLL) return "tile rows reach past pixel row 2^31 - 1";
+    }
     return "";
 }
 

@@ -71,8 +71,8 @@ class Tile:
         return t
 
     def pixel_rows(self, height: int) -> np.ndarray:
-        j = np.arange(self.rows)
-        y = self.y0 + (j // self.band_height) * self.band_stride + j % self.band_height if self.band_height > 0 \
+        j = np.arange(self.rows, dtype=np.int64)  # 64-bit: a refused tile's rows pass 2^31 - 1 (ort_tile)
+        y =self.y0 + (j // self.band_height) * self.band_stride + j % self.band_height if self.band_height > 0 \
             else self.y0 + j
         return y
 

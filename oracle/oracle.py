@@ -111,6 +111,12 @@ def render(spheres, tree, params, x0=0, y0=0, width=None, rows=None, band_height
         sc.n_nodes = t[2].shape[0]
         sc.object_indices = _ip(t[5])
         sc.n_indices = t[5].shape[0]
+    # the row limit of include/ort.h (ort_tile): the last row's pixel row, in Python's integers
+    if rows > 0:
+        j = rows - 1
+        last = y0 + (j // band_height) * band_stride + j % band_height if band_height > 0 else y0 + j
+        if last > 2**31 - 1:
+            raise ValueError(f"oracle.render: tile rows reach past pixel row 2^31 - 1 (last row {last})")
     out = np.empty((rows, width, 3), np.float32)
     cnt = (C.c_uint64 * 6)() if counts else None
     pr = make_params(params)

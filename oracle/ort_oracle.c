@@ -467,6 +467,13 @@ int oracle_render(const oracle_scene* sc, const oracle_params* pr, int x0, int y
                   int band_height, int band_stride, float* out, uint64_t* counts, int nthreads) {
     if (!sc || !pr || !out || tw < 0 || th < 0) return 1;
     if (pr->use_octree == 1 && sc->n_nodes <= 0) return 2;
+    /* the pixel row of the tile's last row must be an int (the row limit of include/ort.h ort_tile) */
+    if (th > 0) {
+        long long j = (long long)th - 1;
+        long long last = band_height > 0 ? (long long)y0 + (j / band_height) * (long long)band_stride + j % band_height
+                                         : (long long)y0 + j;
+        if (last > 0x7fffffffLL) return 3;
+    }
     Camera cam = Camera_initFromViewMatrix(pr->view, pr->camera_position, pr->camera_zoom,
                                            (float)pr->width / (float)pr->height);
     if (counts) memset(counts, 0, sizeof(uint64_t) * ORACLE_COUNT_N);

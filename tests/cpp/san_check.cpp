@@ -110,6 +110,51 @@ void render_case(const char* name, const Scene& s, int depth, int mspn, int w, i
     std::printf("ok %s: %d nodes, %zu indices\n", name, nn, t.idx.size());
 }
 
+// The row limit (include/ort.h ort_tile) on a 48 x 32 frame: `refused` tiles, whose last row's pixel
+// row passes 2^31 - 1, return an error from the emulation and the oracle and leave the output alone
+// (before the limit the row arithmetic overflowed a signed int here); the largest accepted tiles lie
+// wholly past the frame and are all zeros.
+void limit_case(const char* name, const Scene& s, ort_tile tile, bool refused) {
+    Tree t;
+    if (!build(s, 3, 1, t)) {
+        check(false, "octree build", name);
+        return;
+    }
+    const int nn = (int)t.co.size();
+    const ort_params p = camera(48, 32, 2, 2, 1);
+    oracle_scene os{s.cr.data(), s.ma.data(), s.fr.data(), s.n, t.mn.data(), t.mx.data(), t.co.data(),
+                    t.oo.data(), t.cnt.data(), nn, t.idx.data(), (long long)t.idx.size()};
+    oracle_params op;
+    std::memcpy(&op, &p, sizeof op);
+    const size_t n = 3 * (size_t)tile.width * (size_t)tile.rows;
+    std::vector<float> ref(n, -7.0f);
+    const int orc = oracle_render(&os, &op, tile.x0, tile.y0, tile.width, tile.rows, tile.band_height, tile.band_stride,
+                                  ref.data(), nullptr, 1);
+    for (int layout = 0; layout < 2; ++layout) {
+        std::vector<float> out(n, -7.0f);
+        uint64_t cnt[ORT_COUNT_N] = {0};
+        const int e = ort_debug_emulate_render(s.cr.data(), s.ma.data(), s.fr.data(), s.n, t.mn.data(), t.mx.data(),
+                                               t.co.data(), t.oo.data(), t.cnt.data(), nn, t.idx.data(),
+                                               (int64_t)t.idx.size(), layout, &p, &tile, out.data(), cnt);
+        if (refused) {
+            check(e == ORT_ERR_INVALID_ARG, "a tile past the row limit must be refused", name);
+            for (float v : out) check(v == -7.0f, "a refused tile's output was written", name);
+        } else {
+            check(e == ORT_OK, "emulated render", name);
+            for (float v : out) check(v == 0.0f && !std::signbit(v), "rows past the frame are zeros", name);
+            check(cnt[ORT_COUNT_PIXELS] == 0, "no pixel of the tile is inside the frame", name);
+        }
+    }
+    if (refused) {
+        check(orc != 0, "the oracle must refuse a tile past the row limit", name);
+        for (float v : ref) check(v == -7.0f, "the refusing oracle wrote its output", name);
+    } else {
+        check(orc == 0, "oracle render", name);
+        for (float v : ref) check(v == 0.0f && !std::signbit(v), "oracle: rows past the frame are zeros", name);
+    }
+    std::printf("ok %s\n", name);
+}
+
 Scene random_scene(int n, uint32_t seed) {
     Scene s;
     s.n = n;
@@ -151,6 +196,24 @@ int main() {
         s.cr[4 * 10 + 2] = s.cr[2];
         s.cr[4 * 10 + 3] = s.cr[3];
         render_case("coincident + tangent spheres d5 m1", s, 5, 1, 24, 16, 1, 3);
+    }
+    {  // frames at the kernels' unit sizes (tests/shape_sets.py groups A-D): below and around an 8 x 8 wave
+       // block, a 16 x 16 tile and a tile pair; the group emulation's 3 ranks then outnumber the bands
+        const Scene s = random_scene(100, 42);
+        const int shapes[][2] = {{1, 1}, {1, 2}, {2, 1}, {3, 5}, {7, 9}, {8, 8}, {9, 7}, {15, 17}, {16, 16}, {17, 15},
+                                 {31, 1}, {32, 2}, {33, 3}};
+        for (const auto& wh : shapes) {
+            char name[64];
+            std::snprintf(name, sizeof name, "unit size %d x %d, 2 spp 3 bounces", wh[0], wh[1]);
+            render_case(name, s, 4, 1, wh[0], wh[1], 2, 3);
+        }
+        limit_case("refused: y0 + rows past INT_MAX", s, ort_tile{0, 8, 2147483640, 16, 0, 0}, true);
+        limit_case("refused: band stride 2^30, row 2", s, ort_tile{0, 8, 0, 3, 1, 1 << 30}, true);
+        limit_case("refused: band stride INT_MAX", s, ort_tile{0, 8, 40, 4, 2, 2147483647}, true);
+        limit_case("refused: one row past INT_MAX", s, ort_tile{0, 8, 2147483647, 2, 0, 0}, true);
+        limit_case("accepted: one row at INT_MAX", s, ort_tile{0, 8, 2147483647, 1, 0, 0}, false);
+        limit_case("accepted: eight rows up to INT_MAX", s, ort_tile{0, 8, 2147483640, 8, 0, 0}, false);
+        limit_case("accepted: a band tile whose last row is INT_MAX", s, ort_tile{0, 8, 40, 4, 2, 2147483606}, false);
     }
     {  // error paths of the host ABI
         ort_octree* o = nullptr;
