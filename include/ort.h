@@ -883,8 +883,8 @@ const char* ort_version(void);
  * 4-byte aligned, a color_pitch_bytes that is not 0 or a multiple of 4 of at least 12 * width and
  * below 2^31, ORT_PLACE_FRAME, an output that ort_render_ex refuses, on_device disagreeing with
  * output->is_device.  Variance-guided weights for pictures of several samples: ort_denoise_ex.
- * Not in scope: albedo demodulation, temporal reprojection, denoising on an ort_group, banded
- * tiles (their rows are not neighbours in the frame). */
+ * Not in scope: albedo demodulation, denoising on an ort_group, banded tiles (their rows are not
+ * neighbours in the frame).  Temporal reprojection: ort_history_update. */
 #define ORT_DENOISE_SAME_SPHERE 1   /* a tap of another sphere id (a miss among them) adds nothing */
 typedef struct ort_denoise_desc {
     const float*       color;             /* RGB32F, row r at color + r * color_pitch_bytes */
@@ -935,7 +935,8 @@ int ort_last_denoise_ms(ort_ctx* ctx, float* ms);
  * whatever ort_denoise refuses (base.flags may carry ORT_DENOISE_GAMMA here; ort_denoise still
  * refuses it), variance with sigma_variance <= 0 or NaN, sigma_variance != 0 without variance, a
  * variance that is not 4-byte aligned, reserved != 0.  ort_last_denoise_ms covers this call too.
- * Not in scope: temporal reprojection, albedo demodulation, denoising on an ort_group. */
+ * Not in scope: albedo demodulation, denoising on an ort_group.  (Temporal reprojection, which
+ * gives a moving camera's picture a variance to pass here: ort_history_update.) */
 #define ORT_DENOISE_GAMMA 2   /* the output is pow(result, 1/2.2) per channel, then the format */
 typedef struct ort_denoise_desc_ex {
     ort_denoise_desc base;     /* base.flags may carry ORT_DENOISE_GAMMA here */
@@ -944,6 +945,118 @@ typedef struct ort_denoise_desc_ex {
     int32_t reserved[3];       /* 0 */
 } ort_denoise_desc_ex;
 int ort_denoise_ex(ort_ctx* ctx, const ort_denoise_desc_ex* d, const ort_output* output, void* stream);
+
+/* ---- temporal reprojection: a preview's history carried across camera moves ----------------------
+ * An ort_history keeps, per pixel of a width x rows tile, an integrated linear colour, its history
+ * length and two integrated luminance moments.  ort_history_update takes the new frame's linear
+ * one-sample (or few-sample) picture with the pixel-centre rays and hit records of the same pixels
+ * (ort_trace_camera, ORT_CAMERA_PIXEL_CENTRE), finds for every pixel where its surface point was in
+ * the previous update's frame, fetches that history where it is the same sphere, blends the new
+ * sample in and writes the integrated colour, a variance of its luminance (ort_accum_read_moments'
+ * convention: -1.0f = no estimate) and the history length: SVGF's temporal stage (Schied et al.
+ * 2017).  ort_denoise_ex takes the colour and the variance as they are.  The history is owned by
+ * its context and opaque: two ping-pong sets of two 16-byte records per pixel, {r, g, b, n} and
+ * {m1, m2, t, sphere}, 64 bytes per pixel, allocated by ort_history_begin (which launches nothing);
+ * beside them the previous update's ort_params and tile origin and whether there is a previous
+ * frame.  ort_upload_scene, ort_upload_octree_nodes and ort_build_scene make every history of the
+ * context forget its previous frame (sphere ids mean something else); that is no error.  Several
+ * histories may live on one context; an update reads and writes no render, accumulation, query or
+ * denoise state, and needs no scene.
+ * The arithmetic, every operation one float32 operation in this order (no contraction).  The pixel is
+ * column c, tile row j: frame pixel (x, y) = (tile->x0 + c, tile->y0 + j), record index p = j * width
+ * + c.  Primed names belong to the previous update: the camera frame O', LL', hor', ver', w' (origin,
+ * lower left corner, horizontal, vertical, w of Camera_initFromViewMatrix, glsl:176-202, for its
+ * params), its frame size W', H' and tile origin x0', y0'.  lum is ort_denoise_ex's.
+ * dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.  finite(v): neither NaN nor infinite.
+ *   1 row past the frame (y >= height): the records are {0, 0, 0, 0} and {0, 0, 0, sphere -1}; the
+ *     outputs colour 0, variance -1, length 0; no input is read.
+ *   2 sample: s = color[p], l = lum(s), (t, id) = hits[p], (o, d) = rays[p].
+ *   3 the history of the pixel: prev_X for X in r, g, b, m1, m2, n -- or none.
+ *     no previous frame (the first update, after ort_history_reset or a scene upload): none.
+ *     same camera -- width, height, view, camera_position, camera_zoom of params and the tile's x0, y0
+ *       are bitwise those of the previous update: the pixel's own previous record q, nothing
+ *       projected (a resting camera does not resample its history); none unless n_q > 0 and
+ *       sphere_q == id; prev_X = X_q.
+ *     otherwise: e = (o + t * d) - O' per component for a hit (id >= 0), e = d for a miss (the sky
+ *       is at infinity: only a rotation moves it);  z = -dot(e, w'); none unless z > 0;
+ *       k = 10.0f / z;  q = (k * e + O') - LL' per component;
+ *       a = dot(q, hor') / dot(hor', hor');  b = dot(q, ver') / dot(ver', ver') (the denominators
+ *       made once per call);  fx = (a * (float)W' - 0.5f) - (float)x0';  fy = (b * (float)H' - 0.5f)
+ *       - (float)y0';  none unless fx and fy are finite, -1 <= fx < (float)width and -1 <= fy <
+ *       (float)rows;  ix = floorf(fx), wx = fx - ix, iy = floorf(fy), wy = fy - iy.
+ *       The taps are the previous records at column ix + i, row iy + jj, for (i, jj) = (0, 0), (1, 0),
+ *       (0, 1), (1, 1), with w = (i ? wx : 1 - wx) * (jj ? wy : 1 - wy).  A tap counts if it lies in
+ *       the tile (0 <= column < width, 0 <= row < rows), n_q > 0, sphere_q == id (-1 matches -1)
+ *       and, for a hit with depth_tolerance > 0, fabsf(t_q - dist) <= depth_tolerance * dist with
+ *       dist = sqrtf(dot(e, e)).  Over the counting taps in tap order: ws += w; sum_X += w * X_q.
+ *       none unless ws >= 0.01f;  prev_X = sum_X / ws.
+ *   4 blend, with ok = finite(s.r) and finite(s.g) and finite(s.b):
+ *     no history: ok: c = s, m1 = l, m2 = l * l, n = 1;  else c = 0, m1 = m2 = 0, n = 0.
+ *     history: n = ok ? prev_n + 1 : prev_n;  a = 1 / n;  if a < alpha: a = alpha;
+ *       ok: X = prev_X + a * (new_X - prev_X) for r, g, b, m1 (new value l) and m2 (new value l * l);
+ *       else X = prev_X: a sample with a non-finite channel is never blended.
+ *   5 the records {c, n} and {m1, m2, t, id} go to the other set;  out_color = c;  out_length = n;
+ *     out_variance: with history, ne = 1 / a;  v = m2 - m1 * m1;  if v < 0: v = 0;  r = v / (ne - 1);
+ *       the value is r if ne > 1 and r is finite, else -1.0f.  Without history -1.0f.
+ * With alpha = 0 and a resting camera this is the running mean of the samples and, as the variance,
+ * the variance of that mean which ort_accum_read_moments reports.  alpha > 0 bounds the weight of
+ * old samples (an exponential average once 1 / n < alpha).
+ *   params    width, height, view, camera_position, camera_zoom are read (num_samples must be >= 1,
+ *             as for ort_render).
+ *   tile      one band; width and rows are the history's, x0 and y0 may change between updates.
+ *   color     this frame's linear RGB32F picture, row j at color + j * color_pitch_bytes
+ *             (ort_denoise's pitch rule).
+ *   rays, hits  rows * width records, tight, as ort_trace_camera(ORT_CAMERA_PIXEL_CENTRE) writes them
+ *             for the tile.
+ *   out_color, out_variance, out_length  each NULL or tight: 3, 1 and 1 floats per pixel.  All three
+ *             NULL is allowed: the history still advances.
+ * on_device: every pointer is a device pointer on ctx's device; otherwise host pointers, staged
+ * through grow-only buffers of the history's own (counted in device_bytes).  The stream rules are
+ * ort_accum_render's: stream NULL is the context's stream and the call returns when the work is
+ * done; with a stream and device pointers the call returns at once; host pointers always wait.
+ * Updates of one history are ordered by the caller.  A history of no pixels is valid: its updates
+ * launch nothing.  ort_history_reset: the next update has no previous frame (nothing launched).
+ * ort_history_get_info: width, rows, the updates since begin, the last reset or the last scene
+ * upload, and the device memory held.  ort_history_last_update_ms: the last update's kernel from
+ * HIP events on its stream (ORT_ERR_INVALID_ARG before any update launched one).
+ * ort_history_free: a NULL history is ORT_OK; ort_destroy frees what is left.
+ * ORT_ERR_INVALID_ARG, before anything is launched and with the history and the outputs untouched:
+ * NULL arguments, a history of another context, width or rows < 0 or more than 2^30 pixels at
+ * begin, a tile whose width or rows are not the history's, a banded tile (band_height > 0 and
+ * band_height < rows), params or a tile that ort_render refuses, alpha outside [0, 1] or NaN, a
+ * negative or NaN depth_tolerance, flags != 0, reserved != 0, pointers that are not 4-byte aligned,
+ * a color_pitch_bytes that ort_denoise refuses, NULL color, rays or hits for a history of pixels.
+ * Not in scope: histories on an ort_group, normals in the tap test (a sphere id decides it here),
+ * motion of the scene itself, a spatial variance estimate for young pixels (they report -1 and the
+ * filter's variance term is off for them). */
+typedef struct ort_history ort_history;
+typedef struct ort_history_frame {
+    const ort_params*  params;
+    const ort_tile*    tile;
+    const float*       color;             /* linear RGB32F, row j at color + j * color_pitch_bytes */
+    int64_t            color_pitch_bytes; /* 0: tight (12 * width); else a multiple of 4, >= 12 * width, < 2^31 */
+    const ort_ray*     rays;              /* rows * width records, tight (ORT_CAMERA_PIXEL_CENTRE) */
+    const ort_ray_hit* hits;              /* rows * width records, tight */
+    float*             out_color;         /* NULL, or 3 floats per pixel, tight */
+    float*             out_variance;      /* NULL, or 1 float per pixel: -1.0f = no estimate */
+    float*             out_length;        /* NULL, or 1 float per pixel: the history length n */
+    int32_t on_device;                    /* every pointer above but params and tile is a device pointer */
+    float   alpha;                        /* 0 .. 1: the least weight of the new sample */
+    float   depth_tolerance;              /* >= 0; 0: no depth test */
+    int32_t flags;                        /* 0 */
+    int32_t reserved[4];                  /* 0 */
+} ort_history_frame;
+typedef struct ort_history_info {
+    int32_t width, rows;
+    int64_t updates;                      /* since begin, the last reset or the last scene upload */
+    int64_t device_bytes;
+} ort_history_info;
+int ort_history_begin(ort_ctx* ctx, int32_t width, int32_t rows, ort_history** out);
+int ort_history_update(ort_ctx* ctx, ort_history* history, const ort_history_frame* f, void* stream);
+int ort_history_reset(ort_ctx* ctx, ort_history* history);
+int ort_history_get_info(const ort_history* history, ort_history_info* info);
+int ort_history_last_update_ms(ort_ctx* ctx, ort_history* history, float* ms);
+int ort_history_free(ort_ctx* ctx, ort_history* history);
 
 #ifdef __cplusplus
 }

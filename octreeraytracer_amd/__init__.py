@@ -6,10 +6,10 @@ tracer (shaders/octree_fragment_shader.glsl) is replaced by a hand-written HIP k
 behind the C ABI of include/ort.h (libort.so).
 """
 from ._lib import ORT_ERR_TIMEOUT, OrtError, lib
-from .renderer import Accumulation, FrameParams, Renderer, Tile, algorithmic_bytes
+from .renderer import Accumulation, FrameParams, History, Renderer, Tile, algorithmic_bytes
 from .scene import (FlatOctree, SphereSet, build_octree, camera_view, debug_spheres, prebuilt_spheres,
                     random_spheres)
 
-__all__ = ["ORT_ERR_TIMEOUT", "OrtError", "lib", "Accumulation", "FrameParams", "Renderer", "Tile", "algorithmic_bytes", "FlatOctree", "SphereSet",
+__all__ = ["ORT_ERR_TIMEOUT", "OrtError", "lib", "Accumulation", "FrameParams", "History", "Renderer", "Tile", "algorithmic_bytes", "FlatOctree", "SphereSet",
            "build_octree", "camera_view", "debug_spheres", "prebuilt_spheres", "random_spheres"]
 __version__ = "0.1.0"

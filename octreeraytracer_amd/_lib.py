@@ -73,6 +73,8 @@ EXPORTED_SYMBOLS = (
     "ort_denoise", "ort_last_denoise_ms",
     "ort_accum_begin_ex", "ort_accum_read_moments", "ort_denoise_ex",
     "ort_accum_render_adaptive", "ort_accum_read_counts", "ort_accum_adaptive_stats",
+    "ort_history_begin", "ort_history_update", "ort_history_reset", "ort_history_get_info",
+    "ort_history_last_update_ms", "ort_history_free",
 )
 ORT_GROUP_TRANSPORT_RCCL = 0
 ORT_GROUP_TRANSPORT_COPY = 1
@@ -190,6 +192,19 @@ class OrtAccumAdaptiveStats(C.Structure):
                 ("max_count", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class OrtHistoryFrame(C.Structure):
+    _fields_ = [
+        ("params", C.POINTER(OrtParams)), ("tile", C.POINTER(OrtTile)), ("color", C.c_void_p),
+        ("color_pitch_bytes", C.c_int64), ("rays", C.c_void_p), ("hits", C.c_void_p), ("out_color", C.c_void_p),
+        ("out_variance", C.c_void_p), ("out_length", C.c_void_p), ("on_device", C.c_int32), ("alpha", C.c_float),
+        ("depth_tolerance", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32 * 4),
+    ]
+
+
+class OrtHistoryInfo(C.Structure):
+    _fields_ = [("width", C.c_int32), ("rows", C.c_int32), ("updates", C.c_int64), ("device_bytes", C.c_int64)]
+
+
 class OrtSceneInfo(C.Structure):
     _fields_ = [
         ("n_spheres", C.c_int32), ("n_nodes", C.c_int32), ("n_indices", C.c_int64),
@@ -257,6 +272,14 @@ def _declare(lib, debug: str = "none"):
                                                  C.c_int64, C.c_int32, C.POINTER(OrtParams), C.POINTER(OrtTile),
                                                  C.POINTER(OrtAccumAdaptive), C.c_int32, _ip, _fp, _fp]),
         "ort_debug_adaptive_decision": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(OrtAccumAdaptive), _fp, C.c_float]),
+        "ort_history_begin": (C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(_vp)]),
+        "ort_history_update": (C.c_int, [_vp, _vp, C.POINTER(OrtHistoryFrame), _vp]),
+        "ort_history_reset": (C.c_int, [_vp, _vp]),
+        "ort_history_get_info": (C.c_int, [_vp, C.POINTER(OrtHistoryInfo)]),
+        "ort_history_last_update_ms": (C.c_int, [_vp, _vp, _fp]),
+        "ort_history_free": (C.c_int, [_vp, _vp]),
+        "ort_debug_history_update": (C.c_int, [C.POINTER(OrtParams), C.c_int32, C.c_int32, _fp, _fp,
+                                               C.POINTER(OrtHistoryFrame), _fp, _fp]),
         "ort_accum_begin": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(_vp)]),
         "ort_accum_render": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(OrtOutput), _vp]),
         "ort_accum_restart": (C.c_int, [_vp, _vp, C.POINTER(OrtParams)]),
@@ -327,7 +350,8 @@ def _declare(lib, debug: str = "none"):
         if name in ("ort_trace_camera", "ort_trace_rays_ex", "ort_trace_radiance", "ort_denoise",
                     "ort_last_denoise_ms", "ort_accum_begin_ex", "ort_accum_read_moments",
                     "ort_denoise_ex", "ort_accum_render_adaptive", "ort_accum_read_counts",
-                    "ort_accum_adaptive_stats") and debug == "present" and not hasattr(lib, name):
+                    "ort_accum_adaptive_stats", "ort_history_begin", "ort_history_update", "ort_history_reset",
+                    "ort_history_get_info", "ort_history_last_update_ms", "ort_history_free") and debug == "present" and not hasattr(lib, name):
             continue  # an ORT_LIB override of a build from before these calls (A/B runs): calling it raises
         f = getattr(lib, name)
         f.restype = res

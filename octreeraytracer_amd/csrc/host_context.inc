@@ -337,6 +337,7 @@ void each_buffer(SpecBuffers& b, F f) {
 }  // namespace
 
 struct ort_accum;
+struct ort_history;
 struct ort_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -359,6 +360,9 @@ struct ort_ctx {
     // accumulations (ort_accum_*, accum.inc): the live ones, each with its own state, counters and
     // events (ort_destroy frees what is left)
     std::vector<ort_accum*> accums;
+    // histories (ort_history_*, reproject.inc): the live ones, each with its own records, staging and
+    // events (ort_destroy frees what is left)
+    std::vector<ort_history*> histories;
 };
 
 // A frame's samples accumulated over several passes (include/ort.h): the frame and tile it was
@@ -382,6 +386,22 @@ struct ort_accum {
     DevBuf mstage;         // ort_accum_read_moments into host memory: the mean and the variance, tight
     DevBuf alist;          // adaptive: the slots a pass traces, listed by its pre-pass (allocated by the first pass that may hold pixels)
     DevBuf astage;         // adaptive: ort_accum_read_counts into host memory, and the stats reduction's records
+    EventPair ev;
+};
+
+// A preview's history across camera moves (include/ort.h): two ping-pong sets of two 16-byte records
+// per pixel -- {r, g, b, n} and {m1, m2, t, sphere} -- the previous update's frame and tile origin,
+// and whether there is one.  Host pointers are staged through the history's own buffers.
+struct ort_history {
+    ort_ctx* ctx = nullptr;
+    int width = 0, rows = 0;
+    long long updates = 0;  // since begin, ort_history_reset or a scene upload
+    bool has_prev = false;
+    int cur = 0;            // the set the last update wrote
+    ort_params prev_p{};
+    int prev_x0 = 0, prev_y0 = 0;
+    DevBuf rec[2][2];       // [set][0: {r, g, b, n}, 1: {m1, m2, t, sphere}]
+    DevBuf in_color, in_rays, in_hits, out_color, out_var, out_len;  // host pointers' staging (grow-only)
     EventPair ev;
 };
 
@@ -417,6 +437,29 @@ void free_scene(ort_ctx* c) {
     ort::freeGpuTree(c->scene.tree);
     c->scene.has_scene = false;
     c->scene.scene_gen += 1;  // the accumulations begun on this scene are stale (accum.inc)
+    for (ort_history* h : c->histories) {  // ... and sphere ids mean something else: no previous frame
+        h->has_prev = false;
+        h->updates = 0;
+    }
+}
+
+template <class F>
+void each_history_buffer(ort_history* h, F f) {
+    for (auto& set : h->rec)
+        for (DevBuf& b : set) f(b);
+    f(h->in_color);
+    f(h->in_rays);
+    f(h->in_hits);
+    f(h->out_color);
+    f(h->out_var);
+    f(h->out_len);
+}
+
+// A history's device memory and events, and the object (its context's list is the caller's).
+void free_history(ort_history* h) {
+    each_history_buffer(h, [](DevBuf& b) { free_buf(b); });
+    h->ev.destroy();
+    delete h;
 }
 
 // An accumulation's device memory and events, and the object (its context's list is the caller's).
@@ -546,6 +589,8 @@ int ort_destroy(ort_ctx* ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     for (ort_accum* a : ctx->accums) free_accum(a);
     ctx->accums.clear();
+    for (ort_history* h : ctx->histories) free_history(h);
+    ctx->histories.clear();
     free_scene(ctx);
     const auto drop = [](DevBuf& b) { free_buf(b); };
     each_buffer(ctx->pipe, drop);

@@ -112,6 +112,15 @@ int ort_debug_denoise(const ort_denoise_desc* d, const ort_output* output);
 // TEST-ONLY: ort_denoise_ex on the host CPU, as ort_debug_denoise: the variance prefilter, the
 // iterations through denoise_pixel<true> with the variances propagated, the optional gamma.
 int ort_debug_denoise_ex(const ort_denoise_desc_ex* d, const ort_output* output);
+// TEST-ONLY: ort_history_update on the host CPU, stateless: one update through reproject.inc's
+// reproject_pixel, the kernel's own per-pixel function, one pixel after another.  prev_params (NULL: no
+// previous frame), prev_x0, prev_y0: the previous update's params and tile origin; prev_a, prev_b: its
+// record planes {r, g, b, n} and {m1, m2, t, sphere}, 4 floats per pixel each (not read without a
+// previous frame); f: the frame, host pointers (f->on_device 0), the history's shape being its tile's;
+// next_a, next_b receive the next record planes, f's outputs as ort_history_update writes them.  What
+// ort_history_update refuses of a frame is refused here, with everything untouched.
+int ort_debug_history_update(const ort_params* prev_params, int32_t prev_x0, int32_t prev_y0, const float* prev_a,
+                             const float* prev_b, const ort_history_frame* f, float* next_a, float* next_b);
 // TEST-ONLY: finish_pixel(v, 1) -- pow(x, 1/2.2) per channel, ORT_DENOISE_GAMMA's -- of n_pixels RGB
 // triples on the host (ort_powf is not restated in numpy; out may be rgb).
 int ort_debug_gamma(const float* rgb, int64_t n_pixels, float* out);

@@ -2001,3 +2001,6 @@ __global__ void __launch_bounds__(kBlock) k_cam_node(const uint2* node, const ui
 // ort_accum_adaptive_stats): the ort_pixel_paths<..., 5> instances, the counts resolve and the stats
 // reduction, after accum_moments.inc and every other kernel.
 #include "adaptive.inc"
+// Temporal reprojection (ort_history_*, ort_debug_history_update): after denoise.inc, whose helpers it
+// shares, and last, so that every earlier kernel keeps its place.
+#include "reproject.inc"

@@ -111,6 +111,7 @@ void Raytracer::cleanupBuffers() {
     dguides = nullptr;
     dguidesBytes = 0;
     accum = nullptr;  // (ort_destroy frees it)
+    history = nullptr;
     if (ctx) ort_destroy(ctx);
     if (group) ort_group_destroy(group);
     ctx = nullptr;
@@ -380,6 +381,48 @@ int Raytracer::denoise(const Camera& cam, const ort_tile& tile, const float* rgb
         for (int j = real; j < tile.rows; ++j) std::memset(first + (size_t)(j - real) * pitch, 0, rowBytes);
     }
     return ORT_OK;
+}
+
+int Raytracer::reproject(const Camera& cam, const ort_tile& tile, const float* rgb, float* outColor, float* outVariance,
+                         float alpha, float depthTolerance) {
+    if (!ctx && !group && !initialize()) return ORT_ERR_HIP;
+    if (group) return ORT_ERR_UNSUPPORTED;  // histories live on one context
+    if (tile.width < 0 || tile.rows < 0) return ORT_ERR_INVALID_ARG;
+    const size_t n = (size_t)tile.width * (size_t)tile.rows;
+    std::vector<ort_ray> rays(n);
+    std::vector<ort_ray_hit> hits(n);
+    if (n > 0) {
+        const ort_camera_query q = {rays.data(), hits.data(), nullptr, 0, ORT_CAMERA_PIXEL_CENTRE, {0, 0}};
+        const int rc = traceCamera(cam, tile, q);
+        if (rc != ORT_OK) return rc;
+    }
+    if (history && (historyWidth != tile.width || historyRows != tile.rows)) {
+        (void)ort_history_free(ctx, history);
+        history = nullptr;
+    }
+    if (!history) {
+        const int rc = ort_history_begin(ctx, tile.width, tile.rows, &history);
+        if (rc != ORT_OK) return rc;
+        historyWidth = tile.width;
+        historyRows = tile.rows;
+    }
+    const ort_params p = frameParams(cam);
+    ort_history_frame f;
+    std::memset(&f, 0, sizeof f);
+    f.params = &p;
+    f.tile = &tile;
+    f.color = rgb;
+    f.rays = rays.data();
+    f.hits = hits.data();
+    f.out_color = outColor;
+    f.out_variance = outVariance;
+    f.alpha = alpha;
+    f.depth_tolerance = depthTolerance;
+    return ort_history_update(ctx, history, &f, nullptr);
+}
+
+void Raytracer::resetHistory() {
+    if (history && ctx) (void)ort_history_reset(ctx, history);
 }
 
 int Raytracer::render(const Camera& cam, float* rgb) {

@@ -160,6 +160,20 @@ public:
     int denoise(const Camera& cam, const ort_tile& tile, const float* rgb, const float* variance, float sigmaVariance,
                 bool gamma, const ort_output& output, const DenoiseOptions& options = {});
 
+    // The moving camera (include/ort.h ort_history_update): reprojects the history of the tile's
+    // pixels into cam's frame and blends the frame's LINEAR sample picture rgb (tight RGB32F rows:
+    // readMoments' mean, traceRadiance without gamma) in; outColor (nullptr, or 3 floats per pixel)
+    // receives the integrated colour and outVariance (nullptr, or 1 float per pixel; -1: no estimate)
+    // the variance of its luminance, both for denoise(cam, tile, outColor, outVariance, ..., gamma).
+    // The guides are cam's pixel-centre camera query of the tile, traced here.  The history is begun
+    // by the first call and begun again when the tile's width or rows change; resetHistory makes the
+    // next call a first frame.  Host pointers, synchronous; single-device configurations only (a
+    // group: ORT_ERR_UNSUPPORTED).
+    static constexpr float kHistoryAlpha = 0.1f, kHistoryDepthTolerance = 0.1f;  // as Renderer's History.update
+    int reproject(const Camera& cam, const ort_tile& tile, const float* rgb, float* outColor, float* outVariance,
+                  float alpha = kHistoryAlpha, float depthTolerance = kHistoryDepthTolerance);
+    void resetHistory();
+
     // Adaptive sampling (include/ort.h ort_accum_render_adaptive): with setProgressiveAdaptive(true, ...)
     // renderProgressive's accumulation keeps a sample count per pixel (and the moments; the switch
     // starts the accumulation again) and each call traces `samples` more samples only of the pixels
@@ -214,6 +228,8 @@ private:
     int renderRun();               // one frame of run(): into dframe, or into `frame` with readback
     ort_accum* accum = nullptr;    // renderProgressive's accumulation (the context owns it) and its camera
     ort_params accumParams{};
+    ort_history* history = nullptr;  // reproject's history (the context owns it) and its shape
+    int historyWidth = 0, historyRows = 0;
     bool accumMoments = false;     // setProgressiveMoments
     bool accumAdaptive = false;    // setProgressiveAdaptive and its criterion
     float adaptiveThreshold = 0.02f, adaptiveFloor = 0.05f;

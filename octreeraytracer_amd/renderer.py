@@ -347,6 +347,12 @@ class Renderer:
         still noisy; ``step`` traces them all, as on a moments accumulation."""
         return Accumulation(self, params, tile or Tile.full(params), moments, adaptive)
 
+    def history(self, width: int, rows: int) -> "History":
+        """A preview's history across camera moves for tiles of rows x width pixels (ort_history_begin,
+        include/ort.h): allocates 64 bytes per pixel, launches nothing.  ``History.update`` reprojects
+        it into each new frame and blends the frame's sample in."""
+        return History(self, width, rows)
+
     # -- ray queries ------------------------------------------------------------------
     def _device_arg(self, who, x, what, dtype_name, need):
         """The device address of x, a torch CUDA tensor on this device or a pointer (int)."""
@@ -1014,6 +1020,215 @@ class Accumulation:
 DEFAULT_ADAPTIVE_THRESHOLD = 0.02
 DEFAULT_ADAPTIVE_MIN_SAMPLES = 4
 DEFAULT_ADAPTIVE_LUMINANCE_FLOOR = 0.05
+
+
+# History.update's defaults, chosen on the small frames of tests/test_reproject.py:
+# the least weight of a new sample, and the relative depth difference a tap may have.
+DEFAULT_HISTORY_ALPHA = 0.1
+DEFAULT_DEPTH_TOLERANCE = 0.1
+
+
+def _history_guides(who, guides, rows, width, renderer):
+    """(rays address, hits address, objects to keep alive) of guides = (rays, hits or (t, sphere));
+    renderer: None for numpy arrays, else the Renderer whose device the tensors live on."""
+    try:
+        rays, hits = guides
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: guides must be (rays, hits or (t, sphere))") from None
+    n = rows * width
+    if renderer is None:
+        if isinstance(hits, (tuple, list)):
+            t, sph = hits
+            t, sph = np.ascontiguousarray(t, np.float32), np.ascontiguousarray(sph, np.int32)
+            if t.size != n or sph.size != n:
+                raise ValueError(f"{who}: t and sphere must hold {n} pixels each")
+            rec = np.empty((n, 2), np.int32)
+            rec[:, 0] = t.reshape(-1).view(np.int32)
+            rec[:, 1] = sph.reshape(-1)
+            hits = rec
+        if not isinstance(hits, np.ndarray) or hits.dtype != np.int32 or not hits.flags.c_contiguous or hits.size != 2 * n:
+            raise ValueError(f"{who}: hits must be a C-contiguous int32 array of {n} {{t bits, sphere}} records")
+        if not isinstance(rays, np.ndarray) or rays.dtype != np.float32 or not rays.flags.c_contiguous or rays.size != 6 * n:
+            raise ValueError(f"{who}: rays must be a C-contiguous float32 array of 6 x {n} elements")
+        return rays.ctypes.data, hits.ctypes.data, (rays, hits)
+    if isinstance(hits, (tuple, list)):
+        import torch
+        t, sph = hits
+        if t.numel() != n or sph.numel() != n:
+            raise ValueError(f"{who}: t and sphere must hold {n} pixels each")
+        hits = torch.stack((t.contiguous().view(torch.int32).reshape(-1), sph.reshape(-1)), dim=1).contiguous()
+        torch.cuda.current_stream(renderer.device).synchronize()  # (made on torch's stream, read on the call's)
+    if hasattr(hits, "numel") and hits.numel() != 2 * n:
+        raise ValueError(f"{who}: hits must hold {n} {{t bits, sphere}} records")
+    if hasattr(rays, "numel") and rays.numel() != 6 * n:
+        raise ValueError(f"{who}: rays must hold 6 x {n} elements")
+    return (renderer._device_arg(who, rays, "rays", "float32", 24 * n),
+            renderer._device_arg(who, hits, "hits", "int32", 8 * n), (rays, hits))
+
+
+def _history_frame(p, t, color, pitch, rays, hits, width, device, alpha, depth_tolerance):
+    f = L.OrtHistoryFrame()
+    f.params, f.tile = C.pointer(p), C.pointer(t)
+    f.color, f.rays, f.hits = C.c_void_p(color), C.c_void_p(rays), C.c_void_p(hits)
+    f.color_pitch_bytes = 0 if pitch == 12 * width else int(pitch)
+    f.on_device = 1 if device else 0
+    f.alpha = float(DEFAULT_HISTORY_ALPHA if alpha is None else alpha)
+    f.depth_tolerance = float(DEFAULT_DEPTH_TOLERANCE if depth_tolerance is None else depth_tolerance)
+    return f
+
+
+class History:
+    """A preview's history carried across camera moves (``Renderer.history``; ort_history_* in
+    include/ort.h): per pixel an integrated linear colour, its history length and two luminance
+    moments.  ``update`` finds each pixel's surface point in the previous update's frame, fetches
+    that history where it is the same sphere, blends the new sample in and returns the integrated
+    colour and a variance for ``Renderer.denoise``.  A context manager: leaving it frees the state
+    (as ``close`` does; the renderer's ``close`` frees what is left)."""
+
+    def __init__(self, renderer: Renderer, width: int, rows: int):
+        self._r = renderer
+        self._h = C.c_void_p()
+        self.width, self.rows = int(width), int(rows)
+        renderer._check(renderer._lib.ort_history_begin(renderer._ctx, self.width, self.rows, C.byref(self._h)))
+
+    def close(self):
+        if self._h and self._r._ctx:
+            self._r._check(self._r._lib.ort_history_free(self._r._ctx, self._h))
+        self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        i = L.OrtHistoryInfo()
+        self._r._check(self._r._lib.ort_history_get_info(self._h, C.byref(i)))
+        return {"width": i.width, "rows": i.rows, "updates": i.updates, "device_bytes": i.device_bytes}
+
+    def reset(self):
+        """The next update has no previous frame (nothing launched)."""
+        self._r._check(self._r._lib.ort_history_reset(self._r._ctx, self._h))
+
+    def last_update_ms(self) -> float:
+        """The last update's kernel, from HIP events on its stream."""
+        ms = C.c_float()
+        self._r._check(self._r._lib.ort_history_last_update_ms(self._r._ctx, self._h, C.byref(ms)))
+        return ms.value
+
+    def update(self, image, params: FrameParams, tile: Tile | None = None, guides=None, *, alpha: float | None = None,
+               depth_tolerance: float | None = None, variance=True, length=False, out=None, stream=None):
+        """Reproject the history into the frame `params` and blend the frame's sample in
+        (ort_history_update, include/ort.h).
+
+        image: this frame's LINEAR (rows, width, 3) float32 sample picture (``trace_radiance`` without
+        gamma, ``Accumulation.moments``' mean), a numpy array or a torch CUDA tensor on the renderer's
+        device (then everything stays there); rows may be a pitch apart.
+        params, tile: the frame and the tile of the image; the tile has the history's shape, its
+        origin may move between updates.
+        guides: (rays, hits) as ``trace_camera(params, tile, which="pixel_centre", rays=True)`` returns
+        them -- rays (rows, width, 6) float32, hits an int32 array of {t bits, sphere} records or the
+        pair (t, sphere) -- of the image's kind.  None: traced here.
+        alpha: the least weight of the new sample (0: the running mean; default DEFAULT_HISTORY_ALPHA);
+        depth_tolerance: the relative depth difference a tap may have (0: no test; default
+        DEFAULT_DEPTH_TOLERANCE).
+        out: None allocates the (rows, width, 3) integrated colour, an array or tensor receives it,
+        False leaves it out.  variance, length: True allocates the (rows, width) float32 plane -- the
+        variance of the colour's luminance (-1: no estimate), the history length -- an array or tensor
+        receives it, False leaves it out.  Returns colour, variance, length, those that were asked
+        for (one object when it is the only one, None when none).  stream: as ``render``."""
+        who = "History.update"
+        r = self._r
+        device = not isinstance(image, np.ndarray)
+        rows, width, pitch, color = _denoise_image(who, image, r.device if device else None)
+        tile = tile or Tile.full(params)
+        if guides is None:
+            if device:
+                import torch
+                dev = torch.device("cuda", r.device)
+                hits = torch.empty((rows, width, 2), dtype=torch.int32, device=dev)
+                rays = torch.empty((rows, width, 6), dtype=torch.float32, device=dev)
+                r.trace_camera(params, tile, which="pixel_centre", rays=rays, out=hits, stream=stream)
+            else:
+                t_, sph, rays = r.trace_camera(params, tile, which="pixel_centre", rays=True, stream=stream)
+                hits = (t_, sph)
+            guides = (rays, hits)
+        rays_p, hits_p, keep = _history_guides(who, guides, rows, width, r if device else None)
+        is_flag = lambda x: x is None or isinstance(x, (bool, np.bool_))  # noqa: E731
+        n = rows * width
+
+        def plane(x, want_default, last, what):
+            """(address or None, the object returned) of an output plane."""
+            if is_flag(x):
+                if not (want_default if x is None else bool(x)):
+                    return None, None
+                shape = (rows, width, last) if last > 1 else (rows, width)
+                if device:
+                    import torch
+                    x = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", r.device))
+                else:
+                    x = np.empty(shape, np.float32)
+            if device:
+                return r._device_arg(who, x, what, "float32", 4 * last * n), x
+            if not isinstance(x, np.ndarray) or x.dtype != np.float32 or not x.flags.c_contiguous or x.nbytes < 4 * last * n:
+                raise ValueError(f"{who}: {what} must be a C-contiguous float32 numpy array of >= {4 * last * n} bytes")
+            return x.ctypes.data, x
+
+        oc, out = plane(out, True, 3, "out")
+        ov, variance = plane(variance, False, 1, "variance")
+        ol, length = plane(length, False, 1, "length")
+        p, t = params.to_c(), tile.to_c()
+        f = _history_frame(p, t, color, pitch, rays_p, hits_p, width, device, alpha, depth_tolerance)
+        f.out_color = C.c_void_p(oc) if oc is not None else None
+        f.out_variance = C.c_void_p(ov) if ov is not None else None
+        f.out_length = C.c_void_p(ol) if ol is not None else None
+        s = C.c_void_p(int(stream)) if stream else None
+        r._check(r._lib.ort_history_update(r._ctx, self._h, C.byref(f), s))
+        del keep
+        res = tuple(x for x in (out, variance, length) if x is not None)
+        return None if not res else (res[0] if len(res) == 1 else res)
+
+
+def history_update_host(state, image, params: FrameParams, tile: Tile | None = None, guides=None, *,
+                        alpha: float | None = None, depth_tolerance: float | None = None):
+    """TEST-ONLY: ``History.update`` on the host CPU, stateless (ort_debug_history_update: reproject.inc's
+    reproject_pixel, the kernel's own per-pixel function).  state: None (no previous frame), or what
+    the previous call returned first: (params, (x0, y0), a, b) with the record planes a = {r, g, b, n}
+    and b = {m1, m2, t, sphere}, (rows, width, 4) float32 each.  image, guides: numpy arrays as there
+    (guides are needed).  Returns (next state, colour (rows, width, 3), variance, length (rows, width))."""
+    lib = L.analysis_lib()
+    who = "history_update_host"
+    if not isinstance(image, np.ndarray):
+        raise ValueError(f"{who}: image must be a numpy array")
+    rows, width, pitch, color = _denoise_image(who, image, None)
+    tile = tile or Tile.full(params)
+    rays_p, hits_p, keep = _history_guides(who, guides, rows, width, None)
+    p, t = params.to_c(), tile.to_c()
+    f = _history_frame(p, t, color, pitch, rays_p, hits_p, width, False, alpha, depth_tolerance)
+    col = np.empty((rows, width, 3), np.float32)
+    var = np.empty((rows, width), np.float32)
+    length = np.empty((rows, width), np.float32)
+    f.out_color, f.out_variance, f.out_length = (C.c_void_p(x.ctypes.data) for x in (col, var, length))
+    na = np.empty((rows, width, 4), np.float32)
+    nb = np.empty((rows, width, 4), np.float32)
+    if state is None:
+        pp, x0, y0, pa, pb = None, 0, 0, None, None
+    else:
+        prev_params, (x0, y0), pa, pb = state
+        pp = C.byref(prev_params.to_c())
+        pa, pb = np.ascontiguousarray(pa, np.float32), np.ascontiguousarray(pb, np.float32)
+        if pa.size != 4 * rows * width or pb.size != 4 * rows * width:
+            raise ValueError(f"{who}: the state's record planes must hold {rows} x {width} x 4 floats each")
+    L.acheck(lib.ort_debug_history_update(pp, int(x0), int(y0), L.fptr(pa), L.fptr(pb), C.byref(f), L.fptr(na), L.fptr(nb)))
+    del keep
+    return (params, (int(tile.x0), int(tile.y0)), na, nb), col, var, length
 
 
 def _adaptive_defaults(threshold, min_samples, luminance_floor):
