@@ -55,7 +55,7 @@ $(LIB): $(HOST_OBJS) $(HIP_OBJS)
 	@mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -ldl -Wl,-soname,libort.so
 
-EXAMPLES := stats_row trace_rays progressive pick visibility radiance_probe denoise denoise_variance adaptive reproject
+EXAMPLES := stats_row trace_rays progressive pick visibility radiance_probe denoise denoise_variance adaptive reproject reproject_motion
 examples: build/ort_main $(addprefix build/,$(EXAMPLES))
 
 $(addprefix build/,$(EXAMPLES)): build/%: tests/cpp/%.cpp $(LIB) $(HDRS)
@@ -80,7 +80,7 @@ SAN_HOST := $(addprefix $(SANOBJ)/,$(HOST_SRCS:.cpp=.o))
 SAN_HIP := $(SANOBJ)/ort_kernel.o $(SANOBJ)/gpu_build.o $(SANOBJ)/group.o
 HIP_SAN := $(foreach f,address undefined,-Xarch_host -fsanitize=$(f)) -Xarch_host -fno-sanitize-recover=undefined
 
-SAN_PROGS := san_check san_query san_camera san_query_modes san_radiance san_denoise san_denoise_var san_adaptive san_reproject
+SAN_PROGS := san_check san_query san_camera san_query_modes san_radiance san_denoise san_denoise_var san_adaptive san_reproject san_reproject_motion
 define RUN_SAN
 ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 ./build/san/$(1)
 
@@ -109,7 +109,8 @@ $(SANOBJ)/san_check.o: tests/cpp/san_check.cpp $(HDRS) oracle/ort_oracle.h
 # radiance_chain), the denoiser (ort_debug_denoise: denoise.inc denoise_pixel) and variance-guided denoising
 # (ort_debug_denoise_ex, ort_debug_emulate_moments, ort_debug_gamma) and adaptive accumulations (ort_debug_emulate_adaptive,
 # ort_debug_adaptive_decision: adaptive.inc adaptive_traces, and the calls' argument checks) and temporal reprojection
-# (ort_debug_history_update: reproject.inc reproject_pixel, and the update's argument checks) under the same sanitizers
+# (ort_debug_history_update, ort_debug_history_update_ex, ort_debug_history_state: reproject.inc reproject_pixel with and
+# without motion, the histories' state transitions, and the updates' argument checks) under the same sanitizers
 $(SANOBJ)/san_%.o: tests/cpp/san_%.cpp $(HDRS)
 	@mkdir -p $(SANOBJ)
 	$(CLANGXX) $(SAN) -std=c++17 -I$(SRC) -c $< -o $@

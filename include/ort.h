@@ -1027,8 +1027,8 @@ int ort_denoise_ex(ort_ctx* ctx, const ort_denoise_desc_ex* d, const ort_output*
  * negative or NaN depth_tolerance, flags != 0, reserved != 0, pointers that are not 4-byte aligned,
  * a color_pitch_bytes that ort_denoise refuses, NULL color, rays or hits for a history of pixels.
  * Not in scope: histories on an ort_group, normals in the tap test (a sphere id decides it here),
- * motion of the scene itself, a spatial variance estimate for young pixels (they report -1 and the
- * filter's variance term is off for them). */
+ * a spatial variance estimate for young pixels (they report -1 and the filter's variance term is off
+ * for them).  (Motion of the scene itself: ort_history_update_ex with ORT_HISTORY_MOTION.) */
 typedef struct ort_history ort_history;
 typedef struct ort_history_frame {
     const ort_params*  params;
@@ -1057,6 +1057,54 @@ int ort_history_reset(ort_ctx* ctx, ort_history* history);
 int ort_history_get_info(const ort_history* history, ort_history_info* info);
 int ort_history_last_update_ms(ort_ctx* ctx, ort_history* history, float* ms);
 int ort_history_free(ort_ctx* ctx, ort_history* history);
+
+/* ---- temporal reprojection that follows moving spheres ------------------------------------------
+ * ort_history_update_ex is ort_history_update with one optional addition, ORT_HISTORY_MOTION in
+ * base.flags: the caller vouches that sphere ids keep meaning the same spheres across scene
+ * replacements, and a pixel's surface point is moved back with its sphere before it is projected
+ * into the previous camera.  Spheres carry no texture and no orientation, so a translation and a
+ * uniform scale describe a sphere's motion completely.  With base.flags == 0 the call is
+ * ort_history_update bit for bit: records, outputs, state and `updates`.
+ * State a history gains, private, allocated by its first MOTION update:
+ *   the snapshot: the resident scene's sphere_center_radius (upload index order, the order hit
+ *     records use) at the history's last MOTION update, 16 bytes per sphere with the sphere count,
+ *     counted in device_bytes (grow-only), copied device to device on the update's stream behind the
+ *     kernel;
+ *   the stale mark: a scene replacement still leaves the history without a previous frame and with
+ *     updates == 0, but remembers that there was a previous frame and the updates value it had,
+ *     through several replacements in a row.
+ * Any plain update (ort_history_update, or this call with base.flags == 0) drops the snapshot and the
+ * stale mark, and so does ort_history_reset; what those calls do is unchanged.
+ * A MOTION update needs a resident scene.  It first revives the history -- the previous frame counts
+ * as present again and updates goes on from its remembered value -- if the history is stale, has a
+ * snapshot and the snapshot's sphere count equals the resident scene's; with another count there is
+ * no previous frame (no error).  A history that is not stale and has a previous frame but no snapshot
+ * (the update before was a plain one) treats every sphere as unmoved.  The stale mark is dropped.
+ * With now[k] the scene's four floats of sphere k, snap[k] the snapshot's and n the sphere count,
+ * moved(id) is true when there is a snapshot, 0 <= id < n and at least one of the four floats
+ * differs bitwise; an id outside [0, n) reads no sphere and counts as unmoved, as does a miss.
+ * ort_history_update's steps change only here:
+ *   3 same camera applies only where !moved(id); a moved pixel takes the projected route, the
+ *     previous camera being the bitwise same one (a resting camera still follows a moving sphere).
+ *   3 otherwise, for a hit with moved(id): P = o + t * d per component;  s = snap[id].w / now[id].w;
+ *     P' = snap[id].xyz + s * (P - now[id].xyz) per component (one subtraction, one multiplication,
+ *     one addition, no contraction);  e = P' - O';  from z on as there, the depth test included
+ *     (dist = sqrtf(dot(e, e)) against the stored t_q).  A non-finite s makes fx non-finite: none.
+ *   With !moved(id) the arithmetic is ort_history_update's: the pixels of an unmoved sphere and the
+ *   misses are the plain update's bit for bit.
+ * Known limits: the light that a moved sphere casts or blocks on OTHER spheres (reflections,
+ * occlusion of the sky) lags and is bounded only by alpha; a changed material is not seen at all.
+ * ORT_ERR_NO_SCENE, before anything is launched and with the history untouched: ORT_HISTORY_MOTION
+ * without a resident scene.  ORT_ERR_INVALID_ARG: whatever ort_history_update refuses (base.flags
+ * may carry ORT_HISTORY_MOTION here; ort_history_update still refuses it), unknown bits in
+ * base.flags, reserved != 0 in either struct.  ort_history_last_update_ms covers this call's kernel
+ * too (the snapshot copy not).  Not in scope: groups, rotation, a motion-vector output. */
+#define ORT_HISTORY_MOTION 1   /* hit points are moved back with their sphere before they are projected */
+typedef struct ort_history_frame_ex {
+    ort_history_frame base;   /* base.flags may carry ORT_HISTORY_MOTION here; ort_history_update still refuses it */
+    int32_t reserved[4];      /* 0 */
+} ort_history_frame_ex;
+int ort_history_update_ex(ort_ctx* ctx, ort_history* history, const ort_history_frame_ex* f, void* stream);
 
 #ifdef __cplusplus
 }

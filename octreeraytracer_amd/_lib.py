@@ -75,6 +75,7 @@ EXPORTED_SYMBOLS = (
     "ort_accum_render_adaptive", "ort_accum_read_counts", "ort_accum_adaptive_stats",
     "ort_history_begin", "ort_history_update", "ort_history_reset", "ort_history_get_info",
     "ort_history_last_update_ms", "ort_history_free",
+    "ort_history_update_ex",
 )
 ORT_GROUP_TRANSPORT_RCCL = 0
 ORT_GROUP_TRANSPORT_COPY = 1
@@ -106,6 +107,8 @@ ORT_DENOISE_GAMMA = 2  # ort_denoise_ex only
 # ort_accum_begin_ex flags
 ORT_ACCUM_MOMENTS = 1
 ORT_ACCUM_ADAPTIVE = 4  # implies ORT_ACCUM_MOMENTS (2 stays an unknown bit)
+# ort_history_frame_ex.base.flags (ort_history_update_ex)
+ORT_HISTORY_MOTION = 1
 
 
 class OrtParams(C.Structure):
@@ -201,6 +204,10 @@ class OrtHistoryFrame(C.Structure):
     ]
 
 
+class OrtHistoryFrameEx(C.Structure):
+    _fields_ = [("base", OrtHistoryFrame), ("reserved", C.c_int32 * 4)]
+
+
 class OrtHistoryInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("rows", C.c_int32), ("updates", C.c_int64), ("device_bytes", C.c_int64)]
 
@@ -280,6 +287,10 @@ def _declare(lib, debug: str = "none"):
         "ort_history_free": (C.c_int, [_vp, _vp]),
         "ort_debug_history_update": (C.c_int, [C.POINTER(OrtParams), C.c_int32, C.c_int32, _fp, _fp,
                                                C.POINTER(OrtHistoryFrame), _fp, _fp]),
+        "ort_history_update_ex": (C.c_int, [_vp, _vp, C.POINTER(OrtHistoryFrameEx), _vp]),
+        "ort_debug_history_update_ex": (C.c_int, [C.POINTER(OrtParams), C.c_int32, C.c_int32, _fp, _fp,
+                                                  C.POINTER(OrtHistoryFrameEx), _fp, _fp, C.c_int32, _fp, _fp]),
+        "ort_debug_history_state": (C.c_int, [C.POINTER(C.c_int64), C.c_int32, C.c_int32, _ip]),
         "ort_accum_begin": (C.c_int, [_vp, C.POINTER(OrtParams), C.POINTER(OrtTile), C.POINTER(_vp)]),
         "ort_accum_render": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(OrtOutput), _vp]),
         "ort_accum_restart": (C.c_int, [_vp, _vp, C.POINTER(OrtParams)]),
@@ -351,7 +362,8 @@ def _declare(lib, debug: str = "none"):
                     "ort_last_denoise_ms", "ort_accum_begin_ex", "ort_accum_read_moments",
                     "ort_denoise_ex", "ort_accum_render_adaptive", "ort_accum_read_counts",
                     "ort_accum_adaptive_stats", "ort_history_begin", "ort_history_update", "ort_history_reset",
-                    "ort_history_get_info", "ort_history_last_update_ms", "ort_history_free") and debug == "present" and not hasattr(lib, name):
+                    "ort_history_get_info", "ort_history_last_update_ms", "ort_history_free",
+                    "ort_history_update_ex") and debug == "present" and not hasattr(lib, name):
             continue  # an ORT_LIB override of a build from before these calls (A/B runs): calling it raises
         f = getattr(lib, name)
         f.restype = res

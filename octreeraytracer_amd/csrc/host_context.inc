@@ -389,19 +389,60 @@ struct ort_accum {
     EventPair ev;
 };
 
+// What decides whether an update has a previous frame, and its four transitions (pure host code,
+// shared with the test-only ort_debug_history_state).  ort_history_update_ex's ORT_HISTORY_MOTION lets
+// a history survive a scene replacement: the replacement leaves it stale, with the updates value it
+// had, and a MOTION update revives it if it holds a snapshot of as many spheres as the new scene has.
+struct HistoryState {
+    long long updates = 0;        // since begin, ort_history_reset or a scene upload (a revival goes on counting)
+    bool has_prev = false;
+    bool stale = false;           // a scene replacement took a previous frame away ...
+    long long stale_updates = 0;  // ... and `updates` was this
+    bool has_snap = false;        // the last update was a MOTION update: its scene's spheres are kept ...
+    int snap_n = 0;               // ... this many
+
+    void scene_replaced() {
+        if (has_prev) {
+            stale = true;
+            stale_updates = updates;
+        }
+        has_prev = false;
+        updates = 0;
+    }
+    void forget_motion() { stale = has_snap = false; }  // a plain update, ort_history_reset
+    void reset() {
+        forget_motion();
+        has_prev = false;
+        updates = 0;
+    }
+    // A MOTION update on a scene of n spheres begins: the history revived if it may be.  Returns
+    // whether the update reads the snapshot (false: every sphere counts as unmoved).
+    bool motion_begin(int n) {
+        if (stale && has_snap && snap_n == n) {
+            has_prev = true;
+            updates = stale_updates;
+        }
+        stale = false;
+        return has_prev && has_snap && snap_n == n;
+    }
+    void updated() {
+        has_prev = true;
+        updates += 1;
+    }
+};
+
 // A preview's history across camera moves (include/ort.h): two ping-pong sets of two 16-byte records
 // per pixel -- {r, g, b, n} and {m1, m2, t, sphere} -- the previous update's frame and tile origin,
 // and whether there is one.  Host pointers are staged through the history's own buffers.
-struct ort_history {
+struct ort_history : HistoryState {
     ort_ctx* ctx = nullptr;
     int width = 0, rows = 0;
-    long long updates = 0;  // since begin, ort_history_reset or a scene upload
-    bool has_prev = false;
     int cur = 0;            // the set the last update wrote
     ort_params prev_p{};
     int prev_x0 = 0, prev_y0 = 0;
     DevBuf rec[2][2];       // [set][0: {r, g, b, n}, 1: {m1, m2, t, sphere}]
     DevBuf in_color, in_rays, in_hits, out_color, out_var, out_len;  // host pointers' staging (grow-only)
+    DevBuf snap;            // the snapshot: 16 bytes per sphere, upload order (grow-only; the first MOTION update's)
     EventPair ev;
 };
 
@@ -437,10 +478,8 @@ void free_scene(ort_ctx* c) {
     ort::freeGpuTree(c->scene.tree);
     c->scene.has_scene = false;
     c->scene.scene_gen += 1;  // the accumulations begun on this scene are stale (accum.inc)
-    for (ort_history* h : c->histories) {  // ... and sphere ids mean something else: no previous frame
-        h->has_prev = false;
-        h->updates = 0;
-    }
+    // ... and sphere ids mean something else: no previous frame, unless a MOTION update vouches for them
+    for (ort_history* h : c->histories) h->scene_replaced();
 }
 
 template <class F>
@@ -453,6 +492,7 @@ void each_history_buffer(ort_history* h, F f) {
     f(h->out_color);
     f(h->out_var);
     f(h->out_len);
+    f(h->snap);
 }
 
 // A history's device memory and events, and the object (its context's list is the caller's).

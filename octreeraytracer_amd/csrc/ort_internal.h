@@ -121,6 +121,20 @@ int ort_debug_denoise_ex(const ort_denoise_desc_ex* d, const ort_output* output)
 // ort_history_update refuses of a frame is refused here, with everything untouched.
 int ort_debug_history_update(const ort_params* prev_params, int32_t prev_x0, int32_t prev_y0, const float* prev_a,
                              const float* prev_b, const ort_history_frame* f, float* next_a, float* next_b);
+// TEST-ONLY: ort_history_update_ex on the host CPU, stateless, as ort_debug_history_update.  With
+// ORT_HISTORY_MOTION in f->base.flags: now is the scene's sphere_center_radius (n_spheres records of 4
+// floats, upload order; NULL: ORT_ERR_NO_SCENE) and snap the snapshot's (NULL: none, every sphere counts
+// as unmoved), through reproject_pixel<true>; without the flag now, snap and n_spheres are not read
+// and the call is ort_debug_history_update.  What ort_history_update_ex refuses of a frame is refused.
+int ort_debug_history_update_ex(const ort_params* prev_params, int32_t prev_x0, int32_t prev_y0, const float* prev_a,
+                                const float* prev_b, const ort_history_frame_ex* f, const float* now, const float* snap,
+                                int32_t n_spheres, float* next_a, float* next_b);
+// TEST-ONLY: one transition of what decides whether an update has a previous frame (host_context.inc
+// HistoryState, the histories' own): st = {updates, has_prev, stale, the updates a replacement took
+// away, has a snapshot, its sphere count}; op 0: the scene is replaced, 1: ort_history_reset, 2: a plain
+// update, 3: a MOTION update on a scene of n_spheres (reads_snapshot, if not NULL: whether it reads
+// the snapshot; 0 for the other ops).
+int ort_debug_history_state(int64_t* st, int32_t op, int32_t n_spheres, int32_t* reads_snapshot);
 // TEST-ONLY: finish_pixel(v, 1) -- pow(x, 1/2.2) per channel, ORT_DENOISE_GAMMA's -- of n_pixels RGB
 // triples on the host (ort_powf is not restated in numpy; out may be rgb).
 int ort_debug_gamma(const float* rgb, int64_t n_pixels, float* out);

@@ -418,7 +418,38 @@ int Raytracer::reproject(const Camera& cam, const ort_tile& tile, const float* r
     f.out_variance = outVariance;
     f.alpha = alpha;
     f.depth_tolerance = depthTolerance;
-    return ort_history_update(ctx, history, &f, nullptr);
+    if (!historyMotion) return ort_history_update(ctx, history, &f, nullptr);
+    ort_history_frame_ex fx;
+    std::memset(&fx, 0, sizeof fx);
+    fx.base = f;
+    fx.base.flags = ORT_HISTORY_MOTION;
+    return ort_history_update_ex(ctx, history, &fx, nullptr);
+}
+
+void Raytracer::setHistoryMotion(bool on) { historyMotion = on; }
+
+int Raytracer::moveSpheres(const int* indices, const float* centerRadius, int n) {
+    if (!ctx && !group && !initialize()) return ORT_ERR_HIP;
+    if (group) return ORT_ERR_UNSUPPORTED;  // histories live on one context
+    if (n < 0 || (n > 0 && (!indices || !centerRadius))) return ORT_ERR_INVALID_ARG;
+    if (!sceneReady) {
+        setupScene();
+        setupBuffers();
+        if (!sceneReady) return ORT_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < n; ++i)
+        if (indices[i] < 0 || (size_t)indices[i] >= spheres.size()) return ORT_ERR_INVALID_ARG;
+    for (int i = 0; i < n; ++i) {
+        Sphere& s = spheres[(size_t)indices[i]];
+        s.center = ortm::vec3(centerRadius[4 * i], centerRadius[4 * i + 1], centerRadius[4 * i + 2]);
+        s.radius = centerRadius[4 * i + 3];
+    }
+    octree = Octree(octree.getMaxDepth(), octree.getMaxSpheresPerNode());
+    if (!(cfg.gpuBuild && !cfg.debug)) octree.build(spheres, false);
+    if (accum) (void)ort_accum_free(ctx, accum);  // begun on the scene that goes: the frame starts again
+    accum = nullptr;
+    setupBuffers();
+    return sceneReady ? ORT_OK : ORT_ERR_INVALID_ARG;
 }
 
 void Raytracer::resetHistory() {

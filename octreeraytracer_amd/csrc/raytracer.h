@@ -173,6 +173,16 @@ public:
     int reproject(const Camera& cam, const ort_tile& tile, const float* rgb, float* outColor, float* outVariance,
                   float alpha = kHistoryAlpha, float depthTolerance = kHistoryDepthTolerance);
     void resetHistory();
+    // The moving scene (include/ort.h ort_history_update_ex, ORT_HISTORY_MOTION): with
+    // setHistoryMotion(true) reproject's history survives moveSpheres -- sphere k stays sphere k --
+    // and a pixel's surface point is moved back with its sphere before it is projected, a resting
+    // camera included (the switch alone changes no picture: nothing has moved).  moveSpheres gives
+    // the n spheres indices[i] of getSpheres() the centre and radius centerRadius[4 i ..], builds the
+    // octree again (cfg.gpuBuild: on the device) and replaces the resident scene; an accumulation of
+    // renderProgressive starts again.  The animated loop per frame: moveSpheres, one-sample picture,
+    // reproject, denoise.  Single-device configurations only (a group: ORT_ERR_UNSUPPORTED).
+    void setHistoryMotion(bool on);
+    int moveSpheres(const int* indices, const float* centerRadius, int n);
 
     // Adaptive sampling (include/ort.h ort_accum_render_adaptive): with setProgressiveAdaptive(true, ...)
     // renderProgressive's accumulation keeps a sample count per pixel (and the moments; the switch
@@ -230,6 +240,7 @@ private:
     ort_params accumParams{};
     ort_history* history = nullptr;  // reproject's history (the context owns it) and its shape
     int historyWidth = 0, historyRows = 0;
+    bool historyMotion = false;    // setHistoryMotion
     bool accumMoments = false;     // setProgressiveMoments
     bool accumAdaptive = false;    // setProgressiveAdaptive and its criterion
     float adaptiveThreshold = 0.02f, adaptiveFloor = 0.05f;

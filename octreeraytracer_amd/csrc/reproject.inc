@@ -28,6 +28,8 @@ struct ReprojFrame {
     float Wp, Hp;       // (float)W', (float)H'
     float x0p, y0p;     // (float)x0', (float)y0'
     float alpha, depth_tol;
+    int has_snap;       // motion: there is a snapshot of the spheres at the previous update ...
+    int n_sph;          // ... of this many spheres, the resident scene's count
 };
 
 // The pixel's inputs and the previous records.
@@ -38,6 +40,8 @@ struct ReprojIn {
     const int* hits;             // {t bits, sphere} pairs
     const float4* pa;            // previous {r, g, b, n}
     const float4* pb;            // previous {m1, m2, t, sphere}
+    const float4* now;           // motion: the resident scene's {centre, radius}, upload order
+    const float4* snap;          // motion: the snapshot's
 };
 
 struct ReprojPixel {
@@ -48,6 +52,11 @@ struct ReprojPixel {
 ORT_FN float rp_dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 
 // Pixel (c, j) of an update: the next records and the variance (include/ort.h, steps 1 - 5).
+// kMotion (ort_history_update_ex, ORT_HISTORY_MOTION): a hit whose sphere differs bitwise from its
+// snapshot -- two aligned 16-byte gathers keyed by the sphere id, coherent wherever a sphere covers
+// neighbouring pixels -- is moved back with the sphere before it is projected, and never takes the
+// same-camera shortcut.  Without kMotion none of that is compiled.
+template <bool kMotion>
 ORT_FN ReprojPixel reproject_pixel(const ReprojFrame& K, const ReprojIn& I, int c, int j) {
     ReprojPixel R;
     R.var = -1.0f;
@@ -67,7 +76,19 @@ ORT_FN ReprojPixel reproject_pixel(const ReprojFrame& K, const ReprojIn& I, int 
 
     bool have = false;
     float pr = 0.0f, pg = 0.0f, pbl = 0.0f, pm1 = 0.0f, pm2 = 0.0f, pn = 0.0f;
-    if (K.has_prev && K.same) {
+    bool moved = false;
+    float4 now = {0.0f, 0.0f, 0.0f, 0.0f}, snap = {0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (kMotion) {
+        if (K.has_prev && K.has_snap && id >= 0 && id < K.n_sph) {
+            now = I.now[id];
+            snap = I.snap[id];
+            moved = __builtin_bit_cast(int32_t, now.x) != __builtin_bit_cast(int32_t, snap.x) ||
+                    __builtin_bit_cast(int32_t, now.y) != __builtin_bit_cast(int32_t, snap.y) ||
+                    __builtin_bit_cast(int32_t, now.z) != __builtin_bit_cast(int32_t, snap.z) ||
+                    __builtin_bit_cast(int32_t, now.w) != __builtin_bit_cast(int32_t, snap.w);
+        }
+    }
+    if (K.has_prev && K.same && !moved) {
         const float4 qa = I.pa[p], qb = I.pb[p];
         if (qa.w > 0.0f && __builtin_bit_cast(int32_t, qb.w) == id) {
             have = true;
@@ -81,7 +102,12 @@ ORT_FN ReprojPixel reproject_pixel(const ReprojFrame& K, const ReprojIn& I, int 
     } else if (K.has_prev) {
         const float* r = I.rays + 6 * p;
         float ex = r[3], ey = r[4], ez = r[5];
-        if (id >= 0) {
+        if (kMotion && moved) {  // the surface point where its sphere was: P' = snap.xyz + s * (P - now.xyz)
+            const float sc = snap.w / now.w;
+            ex = (snap.x + sc * ((r[0] + t * ex) - now.x)) - K.O[0];
+            ey = (snap.y + sc * ((r[1] + t * ey) - now.y)) - K.O[1];
+            ez = (snap.z + sc * ((r[2] + t * ez) - now.z)) - K.O[2];
+        } else if (id >= 0) {
             ex = (r[0] + t * ex) - K.O[0];
             ey = (r[1] + t * ey) - K.O[1];
             ez = (r[2] + t * ez) - K.O[2];
@@ -192,11 +218,12 @@ struct ReprojArgs {
 };
 
 // Block b: row b / segs, pixels 256 (b % segs) .. of it; a wave's 64 lanes are 64 consecutive pixels.
+template <bool kMotion>
 __global__ void __launch_bounds__(kReprojBlock) ort_reproject(ReprojArgs A) {
     const int row = (int)(blockIdx.x / (unsigned)A.segs);
     const int x = (int)(blockIdx.x - (unsigned)row * (unsigned)A.segs) * kReprojBlock + (int)threadIdx.x;
     if (x >= A.K.W) return;
-    const ReprojPixel R = reproject_pixel(A.K, A.I, x, row);
+    const ReprojPixel R = reproject_pixel<kMotion>(A.K, A.I, x, row);
     const size_t p = (size_t)row * (size_t)A.K.W + (size_t)x;
     A.na[p] = R.a;
     A.nb[p] = R.b;
@@ -211,8 +238,8 @@ __global__ void __launch_bounds__(kReprojBlock) ort_reproject(ReprojArgs A) {
 }
 
 // What ort_history_update refuses of a frame for a history of hw x hrows pixels
-// (ORT_ERR_INVALID_ARG), the emulation too.
-std::string check_history_frame(int hw, int hrows, const ort_history_frame* f) {
+// (ORT_ERR_INVALID_ARG), the emulation too.  flags_allowed: 0, or ort_history_update_ex's bits.
+std::string check_history_frame(int hw, int hrows, const ort_history_frame* f, int32_t flags_allowed = 0) {
     if (!f) return "null frame";
     if (!f->params || !f->tile) return "null params or tile";
     const std::string bad = check_params(f->params, f->tile);  // what ort_render refuses
@@ -222,7 +249,7 @@ std::string check_history_frame(int hw, int hrows, const ort_history_frame* f) {
         return "a banded tile's rows are not neighbours in the frame";
     if (!(f->alpha >= 0.0f && f->alpha <= 1.0f)) return "alpha must be 0 .. 1";
     if (!(f->depth_tolerance >= 0.0f)) return "depth_tolerance must be >= 0";
-    if (f->flags != 0) return "unknown flag bits";
+    if ((f->flags & ~flags_allowed) != 0) return "unknown flag bits";
     for (int r : f->reserved)
         if (r != 0) return "reserved must be 0";
     if (((uintptr_t)f->color & 3) || ((uintptr_t)f->rays & 3) || ((uintptr_t)f->hits & 3) || ((uintptr_t)f->out_color & 3) ||
@@ -276,16 +303,42 @@ ReprojFrame reproj_frame(const ort_params* prev, int prev_x0, int prev_y0, const
     return K;
 }
 
+// ... and what ort_history_update_ex refuses beside it.
+std::string check_history_frame_ex(int hw, int hrows, const ort_history_frame_ex* f) {
+    if (!f) return "null frame";
+    const std::string bad = check_history_frame(hw, hrows, &f->base, ORT_HISTORY_MOTION);
+    if (!bad.empty()) return bad;
+    for (int r : f->reserved)
+        if (r != 0) return "reserved must be 0";
+    return "";
+}
+
 bool history_known(const ort_ctx* ctx, const ort_history* h) {
     return h->ctx == ctx && std::find(ctx->histories.begin(), ctx->histories.end(), h) != ctx->histories.end();
 }
 
-int history_update_impl(ort_ctx* ctx, ort_history* h, const ort_history_frame* f, void* stream) {
+// motion: ORT_HISTORY_MOTION (the caller has seen a resident scene).  The snapshot is taken behind
+// the kernel on the update's stream, for a history of no pixels too.
+int history_update_impl(ort_ctx* ctx, ort_history* h, const ort_history_frame* f, void* stream, bool motion) {
     const size_t W = (size_t)h->width, rows = (size_t)h->rows, n = W * rows;
     const int next = h->cur ^ 1;
+    const int n_sph = motion ? ctx->scene.n_spheres : 0;
+    const size_t snap_bytes = 16 * (size_t)n_sph;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if (n > 0 || snap_bytes > 0) HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (snap_bytes > 0)
+        if (int rc = ensure(ctx, h->snap, snap_bytes)) return rc;
+    bool use_snap = false;
+    if (motion) use_snap = h->motion_begin(n_sph);
+    else h->forget_motion();
+    const auto take_snapshot = [&]() -> int {
+        if (!motion) return ORT_OK;
+        if (snap_bytes > 0) HIPCHK(ctx, hipMemcpyAsync(h->snap.p, ctx->scene.sph_cr.p, snap_bytes, hipMemcpyDeviceToDevice, s));
+        h->has_snap = true;
+        h->snap_n = n_sph;
+        return ORT_OK;
+    };
     if (n > 0) {
-        HIPCHK(ctx, hipSetDevice(ctx->device));
-        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
         const bool host = f->on_device == 0;
         const size_t in_row = 12 * W;
         const size_t in_pitch = f->color_pitch_bytes ? (size_t)f->color_pitch_bytes : in_row;
@@ -309,6 +362,10 @@ int history_update_impl(ort_ctx* ctx, ort_history* h, const ort_history_frame* f
         a.I.hits = host ? (const int*)h->in_hits.p : (const int*)f->hits;
         a.I.pa = (const float4*)h->rec[h->cur][0].p;
         a.I.pb = (const float4*)h->rec[h->cur][1].p;
+        a.K.has_snap = use_snap ? 1 : 0;
+        a.K.n_sph = n_sph;
+        a.I.now = (const float4*)ctx->scene.sph_cr.p;
+        a.I.snap = (const float4*)h->snap.p;
         a.na = (float4*)h->rec[next][0].p;
         a.nb = (float4*)h->rec[next][1].p;
         a.out_color = host ? (f->out_color ? (float*)h->out_color.p : nullptr) : f->out_color;
@@ -317,10 +374,12 @@ int history_update_impl(ort_ctx* ctx, ort_history* h, const ort_history_frame* f
         a.segs = (int)((W + kReprojBlock - 1) / kReprojBlock);
         const long long blocks = (long long)a.segs * (long long)rows;  // at most 2^30: a 1-D grid
         HIPCHK(ctx, h->ev.begin(s));
-        hipLaunchKernelGGL(ort_reproject, dim3((unsigned)blocks), dim3(kReprojBlock), 0, s, a);
+        if (motion) hipLaunchKernelGGL(ort_reproject<true>, dim3((unsigned)blocks), dim3(kReprojBlock), 0, s, a);
+        else hipLaunchKernelGGL(ort_reproject<false>, dim3((unsigned)blocks), dim3(kReprojBlock), 0, s, a);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(ctx, e, "ort_reproject launch");
         HIPCHK(ctx, h->ev.end(s));
+        if (int rc = take_snapshot()) return rc;
         if (host) {
             if (f->out_color) HIPCHK(ctx, hipMemcpyAsync(f->out_color, h->out_color.p, 12 * n, hipMemcpyDeviceToHost, s));
             if (f->out_variance) HIPCHK(ctx, hipMemcpyAsync(f->out_variance, h->out_var.p, 4 * n, hipMemcpyDeviceToHost, s));
@@ -328,19 +387,19 @@ int history_update_impl(ort_ctx* ctx, ort_history* h, const ort_history_frame* f
         }
         // (the records are the history's: the next update is enqueued behind this one by the caller's order)
         h->cur = next;
-        h->has_prev = true;
         h->prev_p = *f->params;
         h->prev_x0 = f->tile->x0;
         h->prev_y0 = f->tile->y0;
-        h->updates += 1;
+        h->updated();
         if (host || !stream) HIPCHK(ctx, hipStreamSynchronize(s));
         return ORT_OK;
     }
-    h->has_prev = true;
+    if (int rc = take_snapshot()) return rc;
     h->prev_p = *f->params;
     h->prev_x0 = f->tile->x0;
     h->prev_y0 = f->tile->y0;
-    h->updates += 1;
+    h->updated();
+    if (motion && snap_bytes > 0 && !stream) HIPCHK(ctx, hipStreamSynchronize(s));
     return ORT_OK;
 }
 
@@ -385,17 +444,34 @@ int ort_history_update(ort_ctx* ctx, ort_history* history, const ort_history_fra
         if (!history_known(ctx, history)) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_history_update: not a history of this context");
         const std::string bad = check_history_frame(history->width, history->rows, f);
         if (!bad.empty()) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_history_update: " + bad);
-        return history_update_impl(ctx, history, f, stream);
+        return history_update_impl(ctx, history, f, stream, false);
     } catch (const std::exception& ex) {
         return fail(ctx, ORT_ERR_INTERNAL, std::string("ort_history_update: ") + ex.what());
+    }
+}
+
+int ort_history_update_ex(ort_ctx* ctx, ort_history* history, const ort_history_frame_ex* f, void* stream) {
+    if (!ctx || !history || !f) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_history_update_ex: null argument");
+    try {
+        if (!history_known(ctx, history))
+            return fail(ctx, ORT_ERR_INVALID_ARG, "ort_history_update_ex: not a history of this context");
+        const std::string bad = check_history_frame_ex(history->width, history->rows, f);
+        if (!bad.empty()) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_history_update_ex: " + bad);
+        const bool motion = (f->base.flags & ORT_HISTORY_MOTION) != 0;
+        if (motion && !ctx->scene.has_scene)
+            return fail(ctx, ORT_ERR_NO_SCENE, "ort_history_update_ex: ORT_HISTORY_MOTION needs a resident scene");
+        ort_history_frame base = f->base;
+        base.flags = 0;
+        return history_update_impl(ctx, history, &base, stream, motion);
+    } catch (const std::exception& ex) {
+        return fail(ctx, ORT_ERR_INTERNAL, std::string("ort_history_update_ex: ") + ex.what());
     }
 }
 
 int ort_history_reset(ort_ctx* ctx, ort_history* history) {
     if (!ctx || !history) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_history_reset: null argument");
     if (!history_known(ctx, history)) return fail(ctx, ORT_ERR_INVALID_ARG, "ort_history_reset: not a history of this context");
-    history->has_prev = false;
-    history->updates = 0;
+    history->reset();
     return ORT_OK;
 }
 
@@ -432,15 +508,18 @@ int ort_history_free(ort_ctx* ctx, ort_history* history) {
     return ORT_OK;
 }
 
+}  // extern "C"
+
 #if ORT_ANALYSIS
-// TEST-ONLY host emulation (ort_internal.h): one update on the CPU, one pixel after another through
-// reproject_pixel.  The record planes are copied into aligned arrays and back.
-int ort_debug_history_update(const ort_params* prev_params, int32_t prev_x0, int32_t prev_y0, const float* prev_a,
-                             const float* prev_b, const ort_history_frame* f, float* next_a, float* next_b) {
+namespace {
+
+// One update on the CPU, one pixel after another through reproject_pixel<kMotion>.  The record planes
+// and the sphere arrays are copied into aligned arrays (and the planes back).  f has been checked.
+template <bool kMotion>
+int debug_history_update(const ort_params* prev_params, int32_t prev_x0, int32_t prev_y0, const float* prev_a,
+                         const float* prev_b, const ort_history_frame* f, const float* now, const float* snap, int32_t n_sph,
+                         float* next_a, float* next_b) {
     try {
-        if (!f || !f->tile) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_history_update: null frame or tile");
-        const std::string bad = check_history_frame(f->tile->width, f->tile->rows, f);
-        if (!bad.empty()) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_history_update: " + bad);
         if (f->on_device) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_history_update: host pointers only");
         const size_t W = (size_t)f->tile->width, rows = (size_t)f->tile->rows, n = W * rows;
         if ((long long)n > kHistoryMaxPixels) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_history_update: at most 2^30 pixels");
@@ -453,8 +532,22 @@ int ort_debug_history_update(const ort_params* prev_params, int32_t prev_x0, int
             std::memcpy(pa.data(), prev_a, 16 * n);
             std::memcpy(pb.data(), prev_b, 16 * n);
         }
-        const ReprojFrame K = reproj_frame(prev_params, prev_x0, prev_y0, f);
+        ReprojFrame K = reproj_frame(prev_params, prev_x0, prev_y0, f);
         ReprojIn I;
+        std::vector<float4> vnow, vsnap;
+        I.now = I.snap = nullptr;
+        if (kMotion) {
+            vnow.resize((size_t)n_sph);
+            if (n_sph > 0) std::memcpy(vnow.data(), now, 16 * (size_t)n_sph);
+            if (snap) {
+                vsnap.resize((size_t)n_sph);
+                if (n_sph > 0) std::memcpy(vsnap.data(), snap, 16 * (size_t)n_sph);
+            }
+            K.has_snap = snap ? 1 : 0;
+            K.n_sph = n_sph;
+            I.now = vnow.data();
+            I.snap = vsnap.data();
+        }
         I.color = reinterpret_cast<const unsigned char*>(f->color);
         I.pitch = f->color_pitch_bytes ? (long long)f->color_pitch_bytes : 12ll * (long long)W;
         I.rays = reinterpret_cast<const float*>(f->rays);
@@ -463,7 +556,7 @@ int ort_debug_history_update(const ort_params* prev_params, int32_t prev_x0, int
         I.pb = pb.data();
         for (size_t j = 0; j < rows; ++j)
             for (size_t c = 0; c < W; ++c) {
-                const ReprojPixel R = reproject_pixel(K, I, (int)c, (int)j);
+                const ReprojPixel R = reproject_pixel<kMotion>(K, I, (int)c, (int)j);
                 const size_t p = j * W + c;
                 na[p] = R.a;
                 nb[p] = R.b;
@@ -485,6 +578,63 @@ int ort_debug_history_update(const ort_params* prev_params, int32_t prev_x0, int
         return fail(nullptr, ORT_ERR_INTERNAL, ex.what());
     }
 }
-#endif  // ORT_ANALYSIS
+
+}  // namespace
+
+extern "C" {
+
+// TEST-ONLY host emulations (ort_internal.h).
+int ort_debug_history_update(const ort_params* prev_params, int32_t prev_x0, int32_t prev_y0, const float* prev_a,
+                             const float* prev_b, const ort_history_frame* f, float* next_a, float* next_b) {
+    if (!f || !f->tile) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_history_update: null frame or tile");
+    const std::string bad = check_history_frame(f->tile->width, f->tile->rows, f);
+    if (!bad.empty()) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_history_update: " + bad);
+    return debug_history_update<false>(prev_params, prev_x0, prev_y0, prev_a, prev_b, f, nullptr, nullptr, 0, next_a, next_b);
+}
+
+int ort_debug_history_update_ex(const ort_params* prev_params, int32_t prev_x0, int32_t prev_y0, const float* prev_a,
+                                const float* prev_b, const ort_history_frame_ex* f, const float* now, const float* snap,
+                                int32_t n_spheres, float* next_a, float* next_b) {
+    if (!f || !f->base.tile) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_history_update_ex: null frame or tile");
+    const std::string bad = check_history_frame_ex(f->base.tile->width, f->base.tile->rows, f);
+    if (!bad.empty()) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_history_update_ex: " + bad);
+    ort_history_frame base = f->base;
+    base.flags = 0;
+    if (!(f->base.flags & ORT_HISTORY_MOTION))
+        return debug_history_update<false>(prev_params, prev_x0, prev_y0, prev_a, prev_b, &base, nullptr, nullptr, 0, next_a, next_b);
+    if (!now) return fail(nullptr, ORT_ERR_NO_SCENE, "ort_debug_history_update_ex: ORT_HISTORY_MOTION needs the scene's spheres");
+    if (n_spheres < 0) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_history_update_ex: negative sphere count");
+    return debug_history_update<true>(prev_params, prev_x0, prev_y0, prev_a, prev_b, &base, now, snap, n_spheres, next_a, next_b);
+}
+
+int ort_debug_history_state(int64_t* st, int32_t op, int32_t n_spheres, int32_t* reads_snapshot) {
+    if (!st || op < 0 || op > 3) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_history_state: null state or unknown op");
+    HistoryState h;
+    h.updates = st[0];
+    h.has_prev = st[1] != 0;
+    h.stale = st[2] != 0;
+    h.stale_updates = st[3];
+    h.has_snap = st[4] != 0;
+    h.snap_n = (int)st[5];
+    bool reads = false;
+    if (op == 0) h.scene_replaced();
+    else if (op == 1) h.reset();
+    else {
+        if (op == 2) h.forget_motion();
+        else reads = h.motion_begin(n_spheres);
+        h.updated();
+        h.has_snap = op == 3;
+        h.snap_n = op == 3 ? n_spheres : h.snap_n;
+    }
+    if (reads_snapshot) *reads_snapshot = reads ? 1 : 0;
+    st[0] = h.updates;
+    st[1] = h.has_prev;
+    st[2] = h.stale;
+    st[3] = h.stale_updates;
+    st[4] = h.has_snap;
+    st[5] = h.snap_n;
+    return ORT_OK;
+}
 
 }  // extern "C"
+#endif  // ORT_ANALYSIS

@@ -1124,9 +1124,15 @@ class History:
         return ms.value
 
     def update(self, image, params: FrameParams, tile: Tile | None = None, guides=None, *, alpha: float | None = None,
-               depth_tolerance: float | None = None, variance=True, length=False, out=None, stream=None):
+               depth_tolerance: float | None = None, variance=True, length=False, out=None, stream=None,
+               motion: bool = False):
         """Reproject the history into the frame `params` and blend the frame's sample in
         (ort_history_update, include/ort.h).
+
+        motion=True (ort_history_update_ex with ORT_HISTORY_MOTION): the history survives ``upload`` and
+        ``build_scene`` of the same spheres at new places -- the caller vouches that sphere k stays
+        sphere k -- and a pixel's surface point is moved back with its sphere before it is projected
+        into the previous frame, a resting camera included.  Needs a resident scene.
 
         image: this frame's LINEAR (rows, width, 3) float32 sample picture (``trace_radiance`` without
         gamma, ``Accumulation.moments``' mean), a numpy array or a torch CUDA tensor on the renderer's
@@ -1190,16 +1196,24 @@ class History:
         f.out_variance = C.c_void_p(ov) if ov is not None else None
         f.out_length = C.c_void_p(ol) if ol is not None else None
         s = C.c_void_p(int(stream)) if stream else None
-        r._check(r._lib.ort_history_update(r._ctx, self._h, C.byref(f), s))
+        if motion:
+            fx = L.OrtHistoryFrameEx()
+            fx.base = f
+            fx.base.flags = L.ORT_HISTORY_MOTION
+            r._check(r._lib.ort_history_update_ex(r._ctx, self._h, C.byref(fx), s))
+        else:
+            r._check(r._lib.ort_history_update(r._ctx, self._h, C.byref(f), s))
         del keep
         res = tuple(x for x in (out, variance, length) if x is not None)
         return None if not res else (res[0] if len(res) == 1 else res)
 
 
 def history_update_host(state, image, params: FrameParams, tile: Tile | None = None, guides=None, *,
-                        alpha: float | None = None, depth_tolerance: float | None = None):
+                        alpha: float | None = None, depth_tolerance: float | None = None, motion=None):
     """TEST-ONLY: ``History.update`` on the host CPU, stateless (ort_debug_history_update: reproject.inc's
-    reproject_pixel, the kernel's own per-pixel function).  state: None (no previous frame), or what
+    reproject_pixel, the kernel's own per-pixel function).  motion: None, or (now, snap) for
+    ``update(motion=True)`` (ort_debug_history_update_ex) -- the scene's (n, 4) float32
+    sphere_center_radius and the one at the previous MOTION update (None: no snapshot).  state: None (no previous frame), or what
     the previous call returned first: (params, (x0, y0), a, b) with the record planes a = {r, g, b, n}
     and b = {m1, m2, t, sphere}, (rows, width, 4) float32 each.  image, guides: numpy arrays as there
     (guides are needed).  Returns (next state, colour (rows, width, 3), variance, length (rows, width))."""
@@ -1226,7 +1240,20 @@ def history_update_host(state, image, params: FrameParams, tile: Tile | None = N
         pa, pb = np.ascontiguousarray(pa, np.float32), np.ascontiguousarray(pb, np.float32)
         if pa.size != 4 * rows * width or pb.size != 4 * rows * width:
             raise ValueError(f"{who}: the state's record planes must hold {rows} x {width} x 4 floats each")
-    L.acheck(lib.ort_debug_history_update(pp, int(x0), int(y0), L.fptr(pa), L.fptr(pb), C.byref(f), L.fptr(na), L.fptr(nb)))
+    if motion is None:
+        L.acheck(lib.ort_debug_history_update(pp, int(x0), int(y0), L.fptr(pa), L.fptr(pb), C.byref(f), L.fptr(na), L.fptr(nb)))
+    else:
+        now, snap = motion
+        now = np.ascontiguousarray(now, np.float32).reshape(-1, 4)
+        if snap is not None:
+            snap = np.ascontiguousarray(snap, np.float32).reshape(-1, 4)
+            if snap.shape != now.shape:
+                raise ValueError(f"{who}: the snapshot must hold the scene's {len(now)} spheres")
+        fx = L.OrtHistoryFrameEx()
+        fx.base = f
+        fx.base.flags = L.ORT_HISTORY_MOTION
+        L.acheck(lib.ort_debug_history_update_ex(pp, int(x0), int(y0), L.fptr(pa), L.fptr(pb), C.byref(fx), L.fptr(now),
+                                                 L.fptr(snap), len(now), L.fptr(na), L.fptr(nb)))
     del keep
     return (params, (int(tile.x0), int(tile.y0)), na, nb), col, var, length
 
