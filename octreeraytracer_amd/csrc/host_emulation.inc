@@ -131,6 +131,12 @@ private:
     std::vector<float> zeros_, fr2_, a_, b_;  // absent materials; the frame pairs; the explicit layout's node arrays
 };
 
+// ort_debug_child_order mode 4: the order tables as device code reads them, one byte a thread (this file
+// is part of analysis builds only: ort_kernel.hip includes it under ORT_ANALYSIS)
+__global__ void k_order_tables(uint8_t* out) {
+    if (threadIdx.x < sizeof(ort::OrderTables)) out[threadIdx.x] = ort::g_order_tables.b[threadIdx.x];
+}
+
 }  // namespace
 
 extern "C" {
@@ -769,6 +775,80 @@ int ort_debug_leaf_dedup(uint64_t* out3, int32_t reset) {
         if (reset) ort::g_leaf_dedup[i] = 0;
     }
     if (out3) out3[2] = (uint64_t)ort::Masks64::kLeafDedup;
+    return ORT_OK;
+}
+
+// The camera walk's two child tests on the host (render_core.h child_drops / child_order_keep).
+int ort_debug_child_order(int32_t mode, const float* in, int64_t n, const float* tmins, int32_t n_tmin,
+                          const float* closests, int32_t n_closest, uint64_t* out) {
+    if (!out) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_child_order: no output");
+    if (mode == 2) {
+        for (int i = 0; i < 5; ++i) {
+            out[i] = ort::g_order_visits[i];
+            if (n) ort::g_order_visits[i] = 0;
+        }
+        out[5] = (uint64_t)ort::Masks64::kOrderBits;
+        return ORT_OK;
+    }
+    if (mode == 3) {  // the host's tables
+        for (int i = 0; i < 128; ++i) out[i] = ort::kOrderTablesHost.b[i];
+        return ORT_OK;
+    }
+    if (mode == 4) {  // the device's (g_order_tables), read by a kernel on the current device
+        uint8_t* d = nullptr;
+        uint8_t t[sizeof(ort::OrderTables)];
+        if (hipMalloc((void**)&d, sizeof(t)) != hipSuccess) return fail(nullptr, ORT_ERR_INTERNAL, "ort_debug_child_order: hipMalloc failed");
+        hipLaunchKernelGGL(k_order_tables, dim3(1), dim3(128), 0, 0, d);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(t, d, sizeof(t), hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        if (e != hipSuccess) return fail(nullptr, ORT_ERR_INTERNAL, "ort_debug_child_order: reading the tables failed");
+        for (int i = 0; i < 128; ++i) out[i] = t[i];
+        return ORT_OK;
+    }
+    if ((mode != 0 && mode != 1) || !in || n < 0) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_child_order: bad args");
+    auto both = [&](const float* v, uint32_t& a, uint32_t& b) {
+        a = ~ort::child_drops(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]) & 0xffu;
+        b = ort::child_order_keep(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]);
+    };
+    if (mode == 0) {
+        for (int64_t i = 0; i < n; ++i) {
+            uint32_t a, b;
+            both(in + 10 * i, a, b);
+            out[2 * i] = a;
+            out[2 * i + 1] = b;
+        }
+        return ORT_OK;
+    }
+    // mode 1: every tN <= tM <= tF per axis from the grid (ascending; ties where the indices are
+    // equal), the folds of every (t_min, closest) pair applied as fast_visit applies them
+    if (!tmins || !closests || n_tmin < 1 || n_closest < 1) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_child_order: bad args");
+    for (int64_t i = 1; i < n; ++i)
+        if (!(in[i - 1] <= in[i])) return fail(nullptr, ORT_ERR_INVALID_ARG, "ort_debug_child_order: grid not ascending");
+    struct Tri { float v[3]; float operator[](int i) const { return v[i]; } };
+    std::vector<Tri> tri;
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t j = i; j < n; ++j)
+            for (int64_t k = j; k < n; ++k) tri.push_back(Tri{{in[i], in[j], in[k]}});
+    for (int i = 0; i < 4; ++i) out[i] = 0;
+    for (const auto& A : tri)
+        for (const auto& B : tri)
+            for (const auto& Cx : tri)
+                for (int32_t ti = 0; ti < n_tmin; ++ti)
+                    for (int32_t ci = 0; ci < n_closest; ++ci) {
+                        const float v[10] = {A[0], B[0], A[1], B[1], A[2], B[2], fmaxf(Cx[0], tmins[ti]), fmaxf(Cx[1], tmins[ti]),
+                                             fminf(Cx[1], closests[ci]), fminf(Cx[2], closests[ci])};
+                        uint32_t a, b;
+                        both(v, a, b);
+                        const bool premise = ort::fmin3(v[4], v[5], v[9]) >= ort::fmax3(v[0], v[1], v[6]);
+                        if (premise) {  // {cases with X >= E, of them the forms disagree,
+                            out[0] += 1;
+                            out[1] += a != b;
+                        } else {  //  cases with X < E, of them child_drops keeps a child}
+                            out[2] += 1;
+                            out[3] += a != 0;
+                        }
+                    }
     return ORT_OK;
 }
 

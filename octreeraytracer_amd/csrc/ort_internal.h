@@ -232,6 +232,24 @@ int ort_debug_leaf_forms(uint64_t* out4, int32_t reset);
 // reset: {tested (trips of leaf_kids), dropped untested by a repeat mask (Masks64::kLeafDedup) on a
 // trip that did not hit, the build's Masks64::kLeafDedup}.
 int ort_debug_leaf_dedup(uint64_t* out3, int32_t reset);
+// TEST-ONLY: the depth <= 8 camera walk's two child tests on the host: render_core.h child_drops (eight
+// min3/max3 tests) and child_order_keep (twelve order bits and the two order tables of
+// render_lds_image.inc), both as kept ranks in the reversed layout (rank 0 at bit 7).
+//   mode 0: in[10 i] = {tNA, tNB, tMA, tMB, tFA, tFB, nN, nF, cN, cF} for n cases;
+//           out[2 i] = child_drops' keep bits, out[2 i + 1] = child_order_keep's.
+//   mode 1: a native sweep: in = an ascending grid of n values; per axis every tN <= tM <= tF from it (ties
+//           included), the three axes crossed with every t_min of tmins[n_tmin] and every closest of
+//           closests[n_closest], folded into the C axis as fast_visit folds them.  out[4] = {cases with
+//           X >= E, of them the two forms disagree, cases with X < E, of them child_drops keeps a child}.
+//   mode 2: the internal-node visits of the host's order-bit walks since the last reset (n != 0 resets):
+//           out[6] = {visits, those breaking tN <= tM <= tF (A, B) or nN <= nF or cN <= cF, those below the
+//           root with X < E, those where the two forms keep different children, internal roots whose
+//           premise X >= E failed under the folds (fast_begin clears their child mask),
+//           Masks64::kOrderBits}.
+//   mode 3: out[128] = the host's order tables, table 0 then table 1; mode 4: the device's (g_order_tables, read by a kernel on
+//           the current device).
+int ort_debug_child_order(int32_t mode, const float* in, int64_t n, const float* tmins, int32_t n_tmin,
+                          const float* closests, int32_t n_closest, uint64_t* out);
 // ANALYSIS-ONLY: ort_debug_walk_steps with production != 0: the non-counting walk's step records
 // (leaf children tested after the build's repeat masks, sphere tests) instead of the counting walk's.
 int64_t ort_debug_walk_steps_ex(const float* sphere_center_radius, const float* sphere_mat_albedo, const float* sphere_fuzz_ri,

@@ -33,6 +33,10 @@ struct Masks64 {  // levels 0..7: trees of depth <= 8
     // children but cost every trip three more instructions and every leaf-children node a second
     // LUT read (profiles/leaf_dedup/ab.md) -- so the walk reads A alone; cam_node keeps B.
     static constexpr bool kLeafDedup = true;
+    // the non-counting walk's child test from twelve order bits and two 64-byte order tables
+    // (child_order_keep, render_lds_image.inc) instead of eight min3/max3 tests (child_drops);
+    // false: child_drops everywhere
+    static constexpr bool kOrderBits = true;
     uint64_t m;
     ORT_FN void clear() { m = 0; }
     ORT_FN bool empty() const { return m == 0; }
@@ -71,6 +75,7 @@ struct Masks96 {  // levels 0..9 (ORT_COMPACT_MAX_DEPTH 10)
     static constexpr bool kPreMid = false;
     static constexpr bool kRevPlanes = false;
     static constexpr bool kPopTable = false;  // (the depth <= 8 image's: Masks64)
+    static constexpr bool kOrderBits = false;  // (the depth <= 8 camera walk's child test: Masks64)
     // the rejected-sphere skip here too: with the kid entry loaded in the pop, C5's camera
     // walk went 17.52 -> 16.41 ms in A/B (no gain while the entry was loaded in the node's step)
     static constexpr bool kKidSkip = true;
@@ -128,6 +133,9 @@ struct FastStateT {
     static_assert(!Masks::kPopTable || (Masks::kRevPlanes && Masks::kInlineLeaves), "the pop table has no level-D entries");
     static_assert(!Masks::kLeafInline || (Masks::kInlineLeaves && !Masks::kKidSkip), "leaf16 records: inline leaf children, no skip");
     static_assert(!Masks::kLeafDedup || Masks::kLeafInline, "repeat masks: the leaf16 records");
+    // (the order tables are device memory, not part of the reversed-plane image -- render_lds_image.inc says
+    // why -- so the trait asks nothing of the image; it asks for the camera walk, whose root fast_begin handles)
+    static_assert(!Masks::kOrderBits || Masks::kLeafDedup, "order bits: the depth <= 8 camera walk (fast_begin's CAM)");
     V3 d;            // original-axis direction (Sphere_hit)
     float ya;        // RN(1 / dot(d, d))
     float oA, oB, oC, iA, iB, iC;  // role-axis origin / 1/d
@@ -213,6 +221,7 @@ struct Masks64Plain : Masks64 {
     static constexpr bool kLeafDedup = false;
     static constexpr bool kPopTable = false;  // pops level-D leaves, which the table does not hold
     static constexpr bool kPreMid = false;
+    static constexpr bool kOrderBits = false;
     static constexpr bool kKidSkip = true;
 };
 // ... reading node records and leaf spheres from the workgroup's LDS copies of nk[] / leaf_sph[]

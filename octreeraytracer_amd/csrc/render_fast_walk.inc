@@ -32,6 +32,15 @@ ORT_FN void fetch_rec(const KScene& S, int i, bool kid, FastStateT<Masks>& st) {
     if (kid) st.kd = fetch_kid(S, i);
 }
 
+#if ORT_ANALYSIS
+// analysis library, host walks only
+// (ort_debug_child_order) internal-node visits of the host's order-bit walks (Masks::kOrderBits):
+// {visits, those breaking tN <= tM <= tF on A or B or nN <= nF or cN <= cF, those below the root
+// with X < E, those where child_order_keep and child_drops keep different children, internal roots
+// whose premise X >= E failed under the folds (fast_begin)}
+inline unsigned long long g_order_visits[5];
+#endif
+
 // Root test and state setup (glsl:296-311).  Returns false when the root box is missed.
 // CAM: the root's record from KScene::cam_node (fetch_rec) -- by default where the walk has repeat
 // masks (Masks::kLeafDedup); 0 for a counting walk, which reads node[] throughout.
@@ -104,6 +113,18 @@ ORT_FN bool fast_begin(const KScene& S, const float* planes, const uint8_t* rank
     st.kc_id = ~0u;
     st.kc_e = 0.0f;
     st.masks.clear();
+    if constexpr (Masks::kOrderBits && (CAM < 0 ? Masks::kLeafDedup : CAM != 0)) {
+        // The order-bit child test (child_order_keep) stands on X >= E under the folds, which the
+        // test below, without them, does not give the root (a box behind t_min, or beyond t_max).
+        // The premise is a condition of the root's visit: where it fails child_drops keeps no
+        // child -- every child's entry is >= E > X >= its exit -- so an internal root loses its
+        // child mask here, once per ray, and its visit keeps none either.
+        const float E = fmax3(st.tNA, st.tNB, fmax_tmin(st.tNC)), X = fmin3(st.tFA, st.tFB, fmin2(st.tFC, t_max));
+#if ORT_ANALYSIS && !defined(__HIP_DEVICE_COMPILE__)
+        g_order_visits[4] += (st.rec.y & ORT_INTERNAL_FLAG) && !(X >= E);
+#endif
+        if ((st.rec.y & ORT_INTERNAL_FLAG) && !(X >= E)) st.rec.y &= ~0xffu;
+    }
     return fmin3(st.tFA, st.tFB, st.tFC) >= fmax3(st.tNA, st.tNB, st.tNC);
 }
 
@@ -200,6 +221,80 @@ ORT_FN uint32_t child_drops(float tNA, float tNB, float tMA, float tMB, float tF
 #undef ORT_CHILD
 #endif
     return drop;
+}
+
+// The same test from twelve order bits (Masks::kOrderBits: the depth <= 8 camera walk's, not the
+// counting kernels'): the kept ranks of the eight children, reversed layout, before the child mask.
+// With E = max3(tNA, tNB, nN), the node's entry, and X = min3(tFA, tFB, cF), its exit, the eight
+// min3/max3 tests of child_drops compare nothing but tMA, tMB, nF, cN with each other and with E
+// and X: the twelve conditions of the order tables (render_lds_image.inc: g_order_tables), a false one killing a fixed
+// set of ranks.  When X >= E, child R passes child_drops' test -- each of its nine (exit, entry)
+// pairs has exit >= entry -- exactly when no false condition kills it (DESIGN.md 4.2 has the
+// proof; it needs tN <= tM <= tF per axis, nN <= nF and cN <= cF, which hold because the planes
+// are read in ray order, the rounding is monotone and the folds are).  X >= E holds at every
+// popped node: its parent kept it by this very test on the same floats, and closest does not
+// change before a hit ends the walk; the root, whose test in fast_begin has no folds, is handled
+// there.  A sign bit per condition (a - b of finite floats: set exactly when a < b, +0 on a tie,
+// child_drops' own rule), six to an index, the first shifted in ending at bit 5; the two table
+// bytes (render_lds_image.inc: g_order_tables) ANDed.  12 x (v_sub + v_alignbit) + v_max3 + v_min3 instead of 8 x (v_max3 + v_min3 +
+// v_sub + v_alignbit).
+ORT_FN void child_order_index(float tNA, float tNB, float tMA, float tMB, float tFA, float tFB, float nN, float nF,
+                              float cN, float cF, uint32_t& i1, uint32_t& i2) {
+    const float E = fmax3(tNA, tNB, nN), X = fmin3(tFA, tFB, cF);
+    uint32_t a = 0, b = 0;
+#define ORT_BIT(I, P, Q) I = (I << 1) | (f2u((P) - (Q)) >> 31);
+    ORT_BIT(a, tMA, E)    //  1: tMA >= E, else no A-near child
+    ORT_BIT(a, tMB, E)    //  2
+    ORT_BIT(a, cN, E)     //  3
+    ORT_BIT(a, X, tMA)    //  4: X >= tMA, else no A-far child
+    ORT_BIT(a, X, tMB)    //  5
+    ORT_BIT(a, X, nF)     //  6
+    ORT_BIT(b, tMA, tMB)  //  7: else none A near and B far
+    ORT_BIT(b, tMB, tMA)  //  8: A far, B near
+    ORT_BIT(b, tMA, nF)   //  9: A near, C far
+    ORT_BIT(b, cN, tMA)   // 10: A far, C near
+    ORT_BIT(b, tMB, nF)   // 11: B near, C far
+    ORT_BIT(b, cN, tMB)   // 12: B far, C near
+#undef ORT_BIT
+    i1 = a;
+    i2 = b;
+}
+ORT_FN uint32_t child_order_keep(float tNA, float tNB, float tMA, float tMB, float tFA, float tFB, float nN, float nF,
+                                 float cN, float cF) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // one asm block, as child_drops is.  Each index opens with a plain shift of its first sign bit
+    // (v_lshrrev: no v_mov 0) and takes five more by v_alignbit; a2 serves as scratch (X) before
+    // its own six bits, e afterwards.  The two table bytes come from g_order_tables (device
+    // memory: two cache lines), the second table 64 bytes behind the first.
+    uint32_t a1, a2;
+    float e;
+#define ORT_B0(I, T, P, Q) "v_sub_f32 " T ", " P ", " Q "\n\tv_lshrrev_b32 " I ", 31, " T "\n\t"
+#define ORT_B(I, T, P, Q) "v_sub_f32 " T ", " P ", " Q "\n\tv_alignbit_b32 " I ", " I ", " T ", 31\n\t"
+    asm("v_max3_f32 %[e], %[NA], %[NB], %[nN]\n\t"
+        ORT_B0("%[a1]", "%[a2]", "%[MA]", "%[e]")
+        ORT_B("%[a1]", "%[a2]", "%[MB]", "%[e]")
+        ORT_B("%[a1]", "%[a2]", "%[cN]", "%[e]")
+        "v_min3_f32 %[a2], %[FA], %[FB], %[cF]\n\t"
+        ORT_B("%[a1]", "%[e]", "%[a2]", "%[MA]")
+        ORT_B("%[a1]", "%[e]", "%[a2]", "%[MB]")
+        ORT_B("%[a1]", "%[e]", "%[a2]", "%[nF]")
+        ORT_B0("%[a2]", "%[e]", "%[MA]", "%[MB]")
+        ORT_B("%[a2]", "%[e]", "%[MB]", "%[MA]")
+        ORT_B("%[a2]", "%[e]", "%[MA]", "%[nF]")
+        ORT_B("%[a2]", "%[e]", "%[cN]", "%[MA]")
+        ORT_B("%[a2]", "%[e]", "%[MB]", "%[nF]")
+        ORT_B("%[a2]", "%[e]", "%[cN]", "%[MB]")
+        : [a1] "=&v"(a1), [a2] "=&v"(a2), [e] "=&v"(e)
+        : [NA] "v"(tNA), [NB] "v"(tNB), [MA] "v"(tMA), [MB] "v"(tMB), [FA] "v"(tFA), [FB] "v"(tFB), [nN] "v"(nN),
+          [nF] "v"(nF), [cN] "v"(cN), [cF] "v"(cF));
+#undef ORT_B0
+#undef ORT_B
+    return (uint32_t)g_order_tables.b[a1] & (uint32_t)g_order_tables.b[(size_t)a2 + 64];  // (64-bit sum: an immediate offset)
+#else
+    uint32_t i1, i2;
+    child_order_index(tNA, tNB, tMA, tMB, tFA, tFB, nN, nF, cN, cF, i1, i2);
+    return (uint32_t)kOrderTablesHost.b[i1] & (uint32_t)kOrderTablesHost.b[64u + i2];
+#endif
 }
 
 // leaf_tests for the inline leaf child `kid` given its leaf16 record lr (Masks::kLeafInline; never
@@ -376,7 +471,21 @@ ORT_FN bool fast_visit(const KScene& S, const uint8_t* rank_lut, FastStateT<Mask
         // exit - entry is never NaN and is +0 when equal: its sign bit is "drop".  The drop
         // bits are shifted in rank order (rank 0 ends at bit 7: the reversed layout) -- one
         // v_max3 + v_min3 + v_sub + v_alignbit per child, no compare/select.
-        const uint32_t keep = rcm & ~child_drops(tNA, tNB, tMA, tMB, tFA, tFB, nN, nF, cN, cF) & 0xffu;
+        // (Masks::kOrderBits, not the counting kernels: the same keep bits from twelve order bits
+        // and two order-table bytes, child_order_keep)
+        uint32_t keep;
+        if constexpr (!COUNT && Masks::kOrderBits) {
+#if ORT_ANALYSIS && !defined(__HIP_DEVICE_COMPILE__)
+            g_order_visits[0] += 1;
+            g_order_visits[1] += !(tNA <= tMA && tMA <= tFA && tNB <= tMB && tMB <= tFB && nN <= nF && cN <= cF);
+            g_order_visits[2] += st.depth > 0 && !(fmin3(tFA, tFB, cF) >= fmax3(tNA, tNB, nN));
+            g_order_visits[3] += (rcm & child_order_keep(tNA, tNB, tMA, tMB, tFA, tFB, nN, nF, cN, cF)) !=
+                                 (rcm & ~child_drops(tNA, tNB, tMA, tMB, tFA, tFB, nN, nF, cN, cF) & 0xffu);
+#endif
+            keep = rcm & child_order_keep(tNA, tNB, tMA, tMB, tFA, tFB, nN, nF, cN, cF);
+        } else {
+            keep = rcm & ~child_drops(tNA, tNB, tMA, tMB, tFA, tFB, nN, nF, cN, cF) & 0xffu;
+        }
         if (Masks::kInlineLeaves && (rec.y & ORT_LEAFKIDS_FLAG)) {
             // Every existing child is a leaf, so the reference pops the surviving ones next,
             // consecutively in rank order (a leaf pushes nothing): test them right here.

@@ -53,6 +53,51 @@ ORT_FN uint32_t pop_table_word(int depth, int table, int hb, int k) {
     if (k == 1) return w4 >> 1;
     return (uint32_t)(((uint64_t)1 << hb) >> (k == 2 ? 0 : 32));
 }
+// The order tables of the depth <= 8 camera walk's child test (Masks64::kOrderBits: child_order_keep):
+// two tables of 64 one-byte entries, back to back.  The walk shifts the "false" bits of conditions
+// 6k+1 .. 6k+6 below into an index, the first at bit 5; entry index of table k is the AND, over the
+// index's set bits, of the complement of that condition's kill set -- rank bits in the reversed
+// layout (rank 0 at bit 7; child of rank R: A far <=> R & 2, B far <=> R & 1, C far <=> R & 4).
+// A condition kills the ranks with all of `far` set and none of `near`:
+//    1 tMA >= E   A near        4 X >= tMA   A far         7 tMA >= tMB  A near, B far   10 cN >= tMA   A far, C near
+//    2 tMB >= E   B near        5 X >= tMB   B far         8 tMB >= tMA  A far, B near   11 tMB >= nF   B near, C far
+//    3 cN >= E    C near        6 X >= nF    C far         9 tMA >= nF   A near, C far   12 cN >= tMB   B far, C near
+// Where the tables live, and why not in the LDS image.  The first form of this test kept them in the
+// image, at bytes 2112-2175 of the axis-0 and axis-1 blocks (the gap before each pop table), read by
+// two ds_read_u8 whose addresses the index registers completed; it measured 5.8 % at C3
+// (profiles/child_order/ab.md).  It was dropped: every byte of the image outside the pop tables is
+// pinned -- planes, rank LUT, zero gaps -- by tests/test_pop_table.py, and the workgroup's LDS has no
+// other free byte at depth 8.  So the tables are 128 bytes of constant device memory (g_order_tables:
+// two cache lines that every wave of a frame shares), read by two global_load_ubyte; the image,
+// lds_bytes and the workgroup's LDS are untouched.  This form measures 4.3 % (same file).  They are
+// declared here, beside the pop table, because they are the walk's other per-scene-constant table.
+constexpr uint32_t order_kill_set(int cond) {  // cond 0..11: condition cond + 1
+    // nibble cond: the axes (A 2, B 1, C 4) on which the killed ranks are the far / the near half
+    const uint32_t far = (uint32_t)(0x142421412000ull >> (4 * cond)) & 7u;
+    const uint32_t near = (uint32_t)(0x414212000412ull >> (4 * cond)) & 7u;
+    uint32_t kill = 0;
+    for (uint32_t R = 0; R < 8; ++R)
+        if ((R & far) == far && (R & near) == 0) kill |= 0x80u >> R;
+    return kill;
+}
+constexpr uint32_t order_table_entry(int table, int index) {
+    uint32_t keep = 0xffu;
+    for (int j = 0; j < 6; ++j)
+        if ((index >> (5 - j)) & 1) keep &= ~order_kill_set(6 * table + j);
+    return keep;
+}
+struct OrderTables {
+    uint8_t b[128];  // table 0, then table 1
+};
+constexpr OrderTables make_order_tables() {
+    OrderTables t{};
+    for (int i = 0; i < 128; ++i) t.b[i] = (uint8_t)order_table_entry(i >> 6, i & 63);
+    return t;
+}
+#if defined(__HIPCC__)
+static __device__ const OrderTables g_order_tables = make_order_tables();
+#endif
+static constexpr OrderTables kOrderTablesHost = make_order_tables();
 struct LdsLayout {
     int lut;     // byte offset of the rank LUT
     int frames;  // byte offset of the frame columns (= the image's size; a multiple of 16)
